@@ -27,10 +27,18 @@ resolve (tonemap on device) and an RCCL gather of the packed 8-bit tiles to
 rank 0.
 
 Also reported: the roofline of the dominant kernel (k_wpath, the persistent
-path engine: closest-hit queries + shading) from in-kernel counters and
-HIP-event launch times, per rank; the reference CPU renderer timed on this
-host (per-config bounded samples, render only); and the wall-clock to PPM of
-the drop-in CLI on the whole config, on N GPUs in one process (PT_NGPU=N).
+path engine: closest-hit queries + shading) from the timed steps' own in-kernel
+counters and HIP-event launch times, per rank.
+
+A plain run does only that: set-up, warm-up, the timed steps, one result line.
+`--dump-outputs DIR` also writes what the last timed step returned (rank 0's
+gathered H x W x 3 framebuffer) as DIR/framebuffer.npy in float32; the scene
+and every pixel's seed are fixed, so two builds can be compared value for value.
+`--full` adds the legs that take runs of their own: the compiler's resource
+report of the kernels (disassembles the objects), the reference CPU renderer
+timed on this host (per-config bounded samples, render only), and the
+wall-clock to PPM of the drop-in CLI on the whole config, on N GPUs in one
+process (PT_NGPU=N), whose PPM the last step's framebuffer is checked against.
 """
 import argparse
 import hashlib
@@ -40,6 +48,7 @@ import re
 import socket
 import subprocess
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -50,6 +59,7 @@ sys.path.insert(0, os.path.join(REPO, "tools"))
 import make_scene  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs writes at most this much
 REF_MD5 = {"c1": "99f1bc9386a22892970f058bfa8114c7", "c2": "a16f6cf46a6443244ecbd0c9d856c295"}
 
 
@@ -65,10 +75,26 @@ def load_ptrace():
     return mod
 
 
-def scene_file(config):
+def gen_dir():
+    """where generated scenes are written: scenes/gen of the tree, or, where the tree is
+    not this user's to write, a per-user directory under the system's temporary one"""
     gen = os.path.join(REPO, "scenes", "gen")
-    os.makedirs(gen, exist_ok=True)
-    p = os.path.join(gen, config + ".txt")
+    try:
+        os.makedirs(gen, exist_ok=True)
+        if os.access(gen, os.W_OK | os.X_OK):
+            return gen
+    except OSError:
+        pass
+    gen = os.path.join(tempfile.gettempdir(), "pt_scenes_gen_%d" % os.getuid())
+    os.makedirs(gen, mode=0o700, exist_ok=True)
+    return gen
+
+
+def scene_file(config):
+    p = os.path.join(REPO, "scenes", "gen", config + ".txt")
+    if os.path.exists(p):
+        return p
+    p = os.path.join(gen_dir(), config + ".txt")
     if not os.path.exists(p):
         tmp = p + ".%d.tmp" % os.getpid()
         make_scene.make(config, tmp)
@@ -228,7 +254,7 @@ def cpu_baseline(pt, args):
             # the same scene text with only the SAMPLES line changed (per-sample work is i.i.d.)
             text = open(src).read()
             text = re.sub(r"(?m)^SAMPLES\s+\d+", "SAMPLES %d" % spp, text, count=1)
-            src = os.path.join(REPO, "scenes", "gen", "%s_spp%d.txt" % (cfg, spp))
+            src = os.path.join(gen_dir(), "%s_spp%d.txt" % (cfg, spp))
             if not os.path.exists(src) or open(src).read() != text:
                 open(src, "w").write(text)
         out_ppm = "/tmp/pt_cpu_%s_%d.ppm" % (name, os.getpid())
@@ -444,8 +470,14 @@ def main():
                          "for c3; strong: of every pixel of the frame; weak: x N per rank)")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="strong (default): the frame's job split over N GPUs; weak: per-GPU work fixed")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-wallclock", action="store_true", help="skip the full-config CLI run (wall_to_ppm)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's framebuffer (what step() returns on rank 0) as "
+                         "DIR/framebuffer.npy (float32, H x W x 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: kernel_resources, cpu_baseline, wall_to_ppm")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the reference CPU renderer")
+    ap.add_argument("--no-wallclock", action="store_true",
+                    help="with --full: skip the full-config CLI run (wall_to_ppm)")
     ap.add_argument("--cpu-configs", nargs="+", default=list(CPU_SAMPLES), choices=list(CPU_SAMPLES))
     ap.add_argument("--traffic-json", default=os.path.join(REPO, "profiles", "traffic.json"))
     ap.add_argument("--traversal", default="replay", choices=["replay", "exact"])
@@ -455,6 +487,8 @@ def main():
     ap.add_argument("--probe-ranks", action="store_true", help=argparse.SUPPRESS)
     argv = sys.argv[1:]
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
@@ -600,16 +634,31 @@ def main():
                             "collective_ranks": dist.get_world_size() if world > 1 else 1,
                             "launched_by": "bench.py --gpus" if os.environ.get("PT_BENCH_SPAWNED") else
                                            ("torch.distributed.run" if world > 1 else "single process")},
-            "kernel_resources": kernel_resources(),
+            "full": args.full,
         }
+        if args.full:
+            res["kernel_resources"] = kernel_resources()
+        if args.dump_outputs:
+            # what the last timed step returned to its caller; the same arguments give the same
+            # scene and per-pixel seeds, so the file is comparable from build to build
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            out = img.astype(np.float32)
+            if out.nbytes > DUMP_MAX_BYTES:
+                # a frame too large to write whole (config 5): a fixed, seeded sample of its pixels
+                n = DUMP_MAX_BYTES // 2 // 12
+                out = out.reshape(-1, 3)[np.sort(np.random.default_rng(0).choice(W * H, n, replace=False))]
+            np.save(os.path.join(args.dump_outputs, "framebuffer.npy"), out)
+            res["dumped_outputs"] = {"framebuffer": list(out.shape)}
         if per_rank:
             res["per_rank"] = per_rank
         res["job_s"] = T / max(args.steps, 1)   # one job (step): the frame's pass, tonemap and gather
     ss.close()
     scene.close()
-    # the host-side legs run after the timed region, on rank 0 only; the other
+    # the host-side legs (--full) run after the timed region, on rank 0 only; the other
     # ranks wait at the final barrier (their GPUs are free for the N-GPU CLI run)
-    if rank == 0:
+    if rank == 0 and not args.full:
+        print(json.dumps(res), flush=True)
+    elif rank == 0:
         if world == 1 and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline(pt, args)

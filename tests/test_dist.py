@@ -143,6 +143,56 @@ def test_bench_refuses_mismatched_world():
     assert "refusing" in err
 
 
+def test_bench_options_full_and_dump_outputs_reach_the_ranks():
+    """`--full` and `--dump-outputs DIR` are accepted and passed on to the ranks that
+    `--gpus N` starts (a rank that did not know them would exit with a usage error)."""
+    rc, out, err = _bench(["--gpus", "2", "--probe-ranks", "--full", "--dump-outputs", "unused"])
+    assert rc == 0, err[-2000:]
+    assert out["probe"] and out["n_gpus"] == 2
+    rc, out, err = _bench(["--gpus", "1", "--steps", "0"])
+    assert rc == 2 and out is None and "--steps" in err
+
+
+def test_bench_generates_scenes_outside_a_tree_it_cannot_write(tmp_path, monkeypatch):
+    """where scenes/gen of the tree cannot be made (a checkout owned by another user),
+    the bench writes its generated scene to a per-user temporary directory instead"""
+    import tempfile
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    tree = tmp_path / "tree"
+    tree.mkdir()
+    (tree / "scenes").write_text("not a directory")   # makedirs fails for any user, root included
+    (tmp_path / "t").mkdir()
+    monkeypatch.setattr(bench, "REPO", str(tree))
+    monkeypatch.setattr(tempfile, "tempdir", str(tmp_path / "t"))
+    p = bench.scene_file("c1")
+    assert p.startswith(str(tmp_path / "t")) and bench.scene_file("c1") == p
+    assert open(p, "rb").read() == open(U.scene_path("c1"), "rb").read()
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_the_last_framebuffer(tmp_path):
+    """A plain run times its steps and nothing else (the legs with runs of their own are
+    behind --full); --dump-outputs writes the last step's framebuffer, which is the image
+    the library renders for the same scene and samples."""
+    rc, out, err = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--spp-per-step", "1",
+                           "--dump-outputs", str(tmp_path / "o")])
+    assert rc == 0, err[-2000:]
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["exactness_errors"] == 0 and out["full"] is False
+    for k in ("cpu_baseline", "wall_to_ppm", "kernel_resources", "framebuffer_equals_cli_ppm"):
+        assert k not in out
+    fb = np.load(tmp_path / "o" / "framebuffer.npy")
+    assert fb.dtype == np.float32 and fb.shape == (1080, 1920, 3)
+    assert U.md5(fb.astype(np.uint8).tobytes()) == out["framebuffer_md5"]
+    pt = U.ptrace()
+    with pt.Scene.load(U.scene_path("c3")) as s:
+        rgb, _, st = s.render(samples=1)
+    assert st["errors"] == 0
+    assert np.array_equal(fb, rgb.astype(np.float32))
+
+
 def test_bench_roofline_counts_the_path_engine_alone(tmp_path):
     """bench.py's k_wpath roofline subtracts the cooperative engine's share
     (pt_stats coop_* fields) from the visit counts, time and launches, and

@@ -9,7 +9,7 @@ if [ "${TESTS:-1}" = "1" ]; then
   tail -2 $O/pytest_gpu.log
 fi
 if [ "${BENCH:-1}" = "1" ]; then
-  timeout -k 10 600 python bench.py --steps 20 --warmup 5 ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err || { echo BENCH_FAIL; tail -20 $O/bench.err; exit 1; }
+  timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err || { echo BENCH_FAIL; tail -20 $O/bench.err; exit 1; }
   python3 -c "
 import json; d=json.load(open('$O/bench.json')); w=d.get('wall_to_ppm') or {}
 print('BENCH', round(d['value']), round(d['ms_per_step'],2), round(d['roofline']['frac'],3), 'r256', d.get('render_256spp_mray_s'), d.get('render_256spp_wall_mray_s'), 'ppm_s', w.get('seconds'), 'teardown', w.get('teardown_s'))"
