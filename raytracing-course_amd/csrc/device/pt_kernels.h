@@ -272,6 +272,8 @@ hipError_t pt_launch_trace(const pt::TraceParams& p, int variant, uint32_t lds_b
 hipError_t pt_launch_wave_start(pt::WaveParams p, hipStream_t s);
 // path engine round: {k_wpath, k_wexact, k_wshade (exact results)}
 // sparse: the end-of-pass kernel (few chains: every step kind and several steps per trip)
+// (neither this nor pt_launch_coop zeroes the round's output counter set: the pass loop does,
+// once per round -- host/rounds.cpp zero_round_out)
 hipError_t pt_launch_path_round(pt::WaveParams p, uint32_t path_grid, uint32_t shade_grid, hipStream_t s, bool sparse,
                                 hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 // the cooperative engine's intake order (WaveParams::order): the round's n work items

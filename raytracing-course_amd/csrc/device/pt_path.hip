@@ -736,8 +736,7 @@ hipError_t pt_preload_kernels_path() {
 
 hipError_t pt_launch_path_round(pt::WaveParams p, uint32_t path_grid, uint32_t shade_grid, hipStream_t s, bool sparse,
                                 hipEvent_t e0, hipEvent_t e1) {
-    hipError_t e = hipMemsetAsync(p.ctl + PT_CTL_SET * (1u - p.parity), 0, 4u * PT_CTL_SET, s);
-    if (e != hipSuccess) return e;
+    hipError_t e;
     p.path = 1u;
     if (e0 && (e = hipEventRecord(e0, s)) != hipSuccess) return e;
     if (sparse)

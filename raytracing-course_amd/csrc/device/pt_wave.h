@@ -47,6 +47,14 @@ __device__ __forceinline__ void push_ray(const WaveParams& P, const RayQ& Q, uin
     Q.ri[qi] = q_prep(P.S, ray);
 }
 
+// The pixel slot of a round's work item gi: carry record gi (a suspended Query, then its
+// slot word) below n_carry, else fresh ray gi - n_carry (its slot in ro.w)
+__device__ __forceinline__ uint32_t carry_slot(const uint32_t* rec) { return rec[sizeof(Query) / 4u]; }
+__device__ __forceinline__ uint32_t work_item_slot(const WaveParams& P, uint32_t gi, uint32_t n_carry) {
+    return gi < n_carry ? carry_slot(P.cq[P.parity] + (size_t)gi * P.carry_words)
+                        : f2u(P.fq[P.parity].ro[gi - n_carry].w);
+}
+
 // A value the optimiser must treat as new at this point: a loop-invariant expression
 // built from it (a per-lane address) is then not hoisted into a VGPR held across the
 // whole persistent loop, where it would spill

@@ -88,9 +88,7 @@ __global__ void __launch_bounds__(256) k_wcamera_merge(WaveParams P) {
 // counting sort of the round's work items (suspended queries, then fresh rays) by
 // their pixels' remaining samples, in PT_ORDER_BUCKETS buckets, most first.
 __device__ __forceinline__ uint32_t coop_order_bucket(const WaveParams& P, uint32_t gi, uint32_t n_carry) {
-    const uint32_t slot = gi < n_carry ? P.cq[P.parity][(size_t)gi * P.carry_words + sizeof(Query) / 4u]
-                                       : f2u(P.fq[P.parity].ro[gi - n_carry].w);
-    const uint32_t done = P.st.rec[2u * slot].w;
+    const uint32_t done = P.st.rec[2u * work_item_slot(P, gi, n_carry)].w;
     const uint32_t rem = done < P.target ? P.target - done : 0u;
     const uint64_t b = (uint64_t)rem * PT_ORDER_BUCKETS / ((uint64_t)P.target + 1u);
     return PT_ORDER_BUCKETS - 1u - (uint32_t)b;   // bucket 0 = the most samples left
@@ -148,7 +146,7 @@ __global__ void __launch_bounds__(256) k_side_take(WaveParams P, uint32_t k, Ray
         const uint32_t* w = P.cq[P.parity] + (size_t)gi * P.carry_words;
         uint32_t* d = side_carry + (size_t)kc * P.carry_words;
         *reinterpret_cast<Ray*>(d) = reinterpret_cast<const Query*>(w)->ray;
-        d[sizeof(Query) / 4u] = w[sizeof(Query) / 4u];
+        d[sizeof(Query) / 4u] = carry_slot(w);
     } else if (keep) {
         const RayQ& F = P.fq[P.parity];
         const uint32_t fi = gi - n_carry;

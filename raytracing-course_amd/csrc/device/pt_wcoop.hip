@@ -137,6 +137,71 @@ __device__ __forceinline__ void lc_add(uint32_t* lc, uint32_t k, bool c, uint32_
 #define QC_CP_PASS
 #endif
 
+// The pieces qc_team and qc_pool share (a lane's work each; one copy, so the two cannot drift).
+// A candidate leaf (phase 2; `act` = the lane has one, `ord` its bundle's ordinal): the
+// bound-free slab test, then the first strict minimum over the leaf's primitives.
+// Returns that primitive (-1: no hit) with `best` its hit, `c` the reference leaf and
+// `ainfo` its ancestor-list info.
+__device__ __forceinline__ int qc_leaf_test(const SceneView& S, bool act, uint32_t ord, const Ray& ray, const f3& inv,
+                                            bool par, uint32_t* lc, uint32_t& c, uint32_t& ainfo, Hit& best) {
+    // a candidate is its leaf's bundle (pt_query.h: the leaf's node box, its primitive
+    // range and its first primitive's compact record): the slab test and the first
+    // primitive's test take one round of independent loads
+    const uint32_t bo = S.o_bundle + PT_BUNDLE_BYTES * ord;
+    const F4 b0 = blob_piece(S, bo), b1 = blob_piece(S, bo + 16u), b2 = blob_piece(S, bo + 32u),
+             b3 = blob_piece(S, bo + 48u), b4 = blob_piece(S, bo + 64u), b5 = blob_piece(S, bo + 80u);
+    c = f2u(b3.x);                         // the reference leaf
+    ainfo = act ? S.anc_info[c] : 0u;
+    Node nd;
+    nd.a = b4;                             // the leaf's node record: {c.xyz, s.x}, {s.y, s.z, first, count}
+    nd.b = F4{b5.x, b5.y, b3.y, b3.z};
+    lc_add(lc, LC_NODES, act);
+    const bool hb = act && qc_slab_hit(nd, ray, inv, par);
+    const uint32_t ref = f2u(b3.y), cnt = hb ? f2u(b3.z) : 0u;
+    best.t = PT_INF;
+    best.n = mk3(0.f, 0.f, 0.f);
+    best.interior = 0u;
+    int lid = -1;
+    lc_add(lc, LC_PTESTS, cnt != 0u);
+    if (cnt) {
+        Hit hh;
+        if (qc_prim_hit_rec(S, ref, b0, b1, b2, F4{b3.w, 0.f, 0.f, 0.f}, ray, hh)) { best = hh; lid = (int)ref; }
+    }
+    for (uint32_t i = 1; __ballot(i < cnt) != 0ull; ++i) {
+        lc_add(lc, LC_PTESTS, i < cnt);
+        if (i < cnt) {
+            Hit hh;
+            if (qc_prim_hit(S, ref + i, ray, hh) && hh.t < best.t) { best = hh; lid = (int)(ref + i); }
+        }
+    }
+    return lid;
+}
+// entry j of a team's hitting-leaf list
+template <uint32_t T>
+__device__ __forceinline__ void qc_hl_store(QcTeamLds<T>& H, uint32_t j, uint32_t c, const Hit& best, int lid,
+                                            uint32_t ainfo) {
+    H.hl[QH_IDX][j] = c;
+    H.hl[QH_T][j] = f2u(best.t);
+    H.hl[QH_LID][j] = (uint32_t)lid;
+    H.hl[QH_NX][j] = f2u(best.n.x);
+    H.hl[QH_NY][j] = f2u(best.n.y);
+    H.hl[QH_NZ][j] = f2u(best.n.z);
+    H.hl[QH_IN][j] = best.interior;
+    H.hl[QH_INFO][j] = ainfo;
+}
+// entry e of wide aux node `node` (phase 1): from the LDS copy of the top nodes, or the blob
+__device__ __forceinline__ void qc_aux_entry(const SceneView& S, const QcScene& Q, uint32_t node, uint32_t e, F4& ea,
+                                             F4& eb) {
+    if (node < QC_TOPN) {
+        ea = Q.top[node * PT_AUXW + e].a;
+        eb = Q.top[node * PT_AUXW + e].b;
+    } else {
+        const uint32_t b = S.o_aux + (node * PT_AUXW + e) * (uint32_t)sizeof(AuxSL);
+        ea = blob_piece(S, b);
+        eb = blob_piece(S, b + 16u);
+    }
+}
+
 // Phases 3-5 of the query, per team (team-uniform arguments; dec = this team decides):
 // the hitting leaves L.hl[0, nh) in reference preorder, each decided on its root path
 // with the bound the recursion carries there; the result as qc_team's.
@@ -289,54 +354,14 @@ __device__ int qc_team(const SceneView& S, const QcScene& Q, QcTeamLds<T>& L, bo
             const uint32_t take = want ? (nc < T ? nc : T) : 0u;
             nc -= take;
             const bool act = tl < take;
-            // a candidate is its leaf's bundle (pt_query.h: the leaf's node box, its primitive
-            // range and its first primitive's compact record): the slab test and the first
-            // primitive's test take one round of independent loads
-            const uint32_t ord = act ? L.cand[nc + tl] : 0u;
-            const uint32_t bo = S.o_bundle + PT_BUNDLE_BYTES * ord;
-            const F4 b0 = blob_piece(S, bo), b1 = blob_piece(S, bo + 16u), b2 = blob_piece(S, bo + 32u),
-                     b3 = blob_piece(S, bo + 48u), b4 = blob_piece(S, bo + 64u), b5 = blob_piece(S, bo + 80u);
-            const uint32_t c = f2u(b3.x);          // the reference leaf
-            const uint32_t ainfo = act ? S.anc_info[c] : 0u;
-            Node nd;
-            nd.a = b4;                             // the leaf's node record: {c.xyz, s.x}, {s.y, s.z, first, count}
-            nd.b = F4{b5.x, b5.y, b3.y, b3.z};
-            lc_add(lc, LC_NODES, act);
-            const bool hb = act && qc_slab_hit(nd, ray, inv, par);
-            const uint32_t ref = f2u(b3.y), cnt = hb ? f2u(b3.z) : 0u;
+            uint32_t c, ainfo;
             Hit best;
-            best.t = PT_INF;
-            best.n = mk3(0.f, 0.f, 0.f);
-            best.interior = 0u;
-            int lid = -1;
-            lc_add(lc, LC_PTESTS, cnt != 0u);
-            if (cnt) {
-                Hit hh;
-                if (qc_prim_hit_rec(S, ref, b0, b1, b2, F4{b3.w, 0.f, 0.f, 0.f}, ray, hh)) { best = hh; lid = (int)ref; }
-            }
-            for (uint32_t i = 1; __ballot(i < cnt) != 0ull; ++i) {
-                lc_add(lc, LC_PTESTS, i < cnt);
-                if (i < cnt) {
-                    Hit hh;
-                    if (qc_prim_hit(S, ref + i, ray, hh) && hh.t < best.t) { best = hh; lid = (int)(ref + i); }
-                }
-            }
+            const int lid = qc_leaf_test(S, act, act ? L.cand[nc + tl] : 0u, ray, inv, par, lc, c, ainfo, best);
             const unsigned long long m = __ballot(lid >= 0) & tmask;
             const uint32_t nm = (uint32_t)__popcll(m);
             if (want) {
-                if (nh + nm > HCAP) {
-                    ovf = true;
-                } else if (lid >= 0) {
-                    const uint32_t j = nh + lanes_below(m);
-                    L.hl[QH_IDX][j] = c;
-                    L.hl[QH_T][j] = f2u(best.t);
-                    L.hl[QH_LID][j] = (uint32_t)lid;
-                    L.hl[QH_NX][j] = f2u(best.n.x);
-                    L.hl[QH_NY][j] = f2u(best.n.y);
-                    L.hl[QH_NZ][j] = f2u(best.n.z);
-                    L.hl[QH_IN][j] = best.interior;
-                    L.hl[QH_INFO][j] = ainfo;
-                }
+                if (nh + nm > HCAP) ovf = true;
+                else if (lid >= 0) qc_hl_store(L, nh + lanes_below(m), c, best, lid, ainfo);
                 nh += nm;
             }
             QC_TICK(1);
@@ -364,14 +389,7 @@ __device__ int qc_team(const SceneView& S, const QcScene& Q, QcTeamLds<T>& L, bo
                 act[j] = ni < k;
                 const uint32_t node = act[j] ? L.stk[ns + ni] : 0u;
                 lc_add(lc, LC_AUX, act[j] && e == 0u);
-                if (node < QC_TOPN) {
-                    ea[j] = Q.top[node * PT_AUXW + e].a;
-                    eb[j] = Q.top[node * PT_AUXW + e].b;
-                } else {
-                    const uint32_t b = S.o_aux + (node * PT_AUXW + e) * (uint32_t)sizeof(AuxSL);
-                    ea[j] = blob_piece(S, b);
-                    eb[j] = blob_piece(S, b + 16u);
-                }
+                qc_aux_entry(S, Q, node, e, ea[j], eb[j]);
             }
 #pragma unroll
             for (uint32_t j = 0; j < QC_EPL; ++j) {
@@ -444,52 +462,15 @@ __device__ int qc_pool(const SceneView& S, const QcScene& Q, QcPoolLds<T>& W, Qc
             Ray ir;
             ir.o = mk3(q0.x, q0.y, q0.z);
             ir.d = mk3(q1.x, q1.y, q1.z);
-            const f3 iinv = mk3(q2.x, q2.y, q2.z);
-            const uint32_t ord = act ? item & QcPoolLds<T>::MASK : 0u;
-            const uint32_t bo = S.o_bundle + PT_BUNDLE_BYTES * ord;
-            const F4 b0 = blob_piece(S, bo), b1 = blob_piece(S, bo + 16u), b2 = blob_piece(S, bo + 32u),
-                     b3 = blob_piece(S, bo + 48u), b4 = blob_piece(S, bo + 64u), b5 = blob_piece(S, bo + 80u);
-            const uint32_t c = f2u(b3.x);          // the reference leaf
-            const uint32_t ainfo = act ? S.anc_info[c] : 0u;
-            Node nd;
-            nd.a = b4;                             // the leaf's node record: {c.xyz, s.x}, {s.y, s.z, first, count}
-            nd.b = F4{b5.x, b5.y, b3.y, b3.z};
-            lc_add(lc, LC_NODES, act);
-            const bool hb = act && qc_slab_hit(nd, ir, iinv, signbit(q0.w));
-            const uint32_t ref = f2u(b3.y), cnt = hb ? f2u(b3.z) : 0u;
+            uint32_t c, ainfo;
             Hit best;
-            best.t = PT_INF;
-            best.n = mk3(0.f, 0.f, 0.f);
-            best.interior = 0u;
-            int lid = -1;
-            lc_add(lc, LC_PTESTS, cnt != 0u);
-            if (cnt) {
-                Hit hh;
-                if (qc_prim_hit_rec(S, ref, b0, b1, b2, F4{b3.w, 0.f, 0.f, 0.f}, ir, hh)) { best = hh; lid = (int)ref; }
-            }
-            for (uint32_t i = 1; __ballot(i < cnt) != 0ull; ++i) {
-                lc_add(lc, LC_PTESTS, i < cnt);
-                if (i < cnt) {
-                    Hit hh;
-                    if (qc_prim_hit(S, ref + i, ir, hh) && hh.t < best.t) { best = hh; lid = (int)(ref + i); }
-                }
-            }
+            const int lid = qc_leaf_test(S, act, act ? item & QcPoolLds<T>::MASK : 0u, ir, mk3(q2.x, q2.y, q2.z),
+                                         signbit(q0.w), lc, c, ainfo, best);
             if (lid >= 0) {
                 // (distinct leaves: the list's order is free)
                 const uint32_t j = atomicAdd(&W.nh[ch], 1u);
-                if (j < HCAP) {
-                    QcTeamLds<T>& H = Lw[ch];
-                    H.hl[QH_IDX][j] = c;
-                    H.hl[QH_T][j] = f2u(best.t);
-                    H.hl[QH_LID][j] = (uint32_t)lid;
-                    H.hl[QH_NX][j] = f2u(best.n.x);
-                    H.hl[QH_NY][j] = f2u(best.n.y);
-                    H.hl[QH_NZ][j] = f2u(best.n.z);
-                    H.hl[QH_IN][j] = best.interior;
-                    H.hl[QH_INFO][j] = ainfo;
-                } else {
-                    W.ovf[ch] = 1u;                // more hitting leaves than the list: the exact DFS
-                }
+                if (j < HCAP) qc_hl_store(Lw[ch], j, c, best, lid, ainfo);
+                else W.ovf[ch] = 1u;               // more hitting leaves than the list: the exact DFS
             }
             QC_TICK(1);
         }
@@ -511,14 +492,7 @@ __device__ int qc_pool(const SceneView& S, const QcScene& Q, QcPoolLds<T>& W, Qc
         const bool act = ni < k && W.ovf[ch] == 0u;
         lc_add(lc, LC_AUX, act && e == 0u);
         F4 ea, eb;
-        if (node < QC_TOPN) {
-            ea = Q.top[node * PT_AUXW + e].a;
-            eb = Q.top[node * PT_AUXW + e].b;
-        } else {
-            const uint32_t bo = S.o_aux + (node * PT_AUXW + e) * (uint32_t)sizeof(AuxSL);
-            ea = blob_piece(S, bo);
-            eb = blob_piece(S, bo + 16u);
-        }
+        qc_aux_entry(S, Q, node, e, ea, eb);
         const F4 q0 = W.ray[ch][0], q1 = W.ray[ch][1], q2 = W.ray[ch][2], q3 = W.ray[ch][3];
         Ray ir;
         ir.o = mk3(q0.x, q0.y, q0.z);
@@ -600,6 +574,72 @@ __device__ __forceinline__ bool coop_shade(const WaveParams& P, const QcScene& Q
         }
     }
     return emit;
+}
+
+// Work item gi of a launch's input (pt_wave.h work_item_slot) as a query at its start:
+// its ray, pixel slot, plane result and query set-up.  Returns whether it is a fresh ray
+// (which whoever takes it counts).
+template <bool BIG>
+__device__ __forceinline__ bool coop_item(const WaveParams& P, const QcScene& Q, const RayQ& FQ, uint32_t gi,
+                                          uint32_t n_carry, Ray& ray, uint32_t& slot, float& Pt, int& pid, F4& pre) {
+    if (gi < n_carry) {
+        // a query suspended by the path engine: restarted from its ray (a query is a
+        // function of the ray alone; its ray and plane tests were counted when taken)
+        const uint32_t* w = P.cq[P.parity] + (size_t)gi * P.carry_words;
+        ray = reinterpret_cast<const Query*>(w)->ray;
+        slot = carry_slot(w);
+        q_planes_e(P.S, PlanesLds<BIG>{Q, P.S}, ray, Pt, pid);
+        pre = q_prep(P.S, ray);
+        return false;
+    }
+    const uint32_t fi = gi - n_carry;
+    const F4 o = FQ.ro[fi], d = FQ.rd[fi];
+    ray.o = mk3(o.x, o.y, o.z);
+    ray.d = mk3(d.x, d.y, d.z);
+    slot = f2u(o.w);
+    Pt = d.w;
+    pid = FQ.pid[fi];
+    pre = FQ.ri[fi];
+    return true;
+}
+// a chain's pixel state (its team's first lane) back to HBM
+template <class TL>
+__device__ __forceinline__ void coop_store_pixel(const WaveParams& P, const TL& L, const CoopPixel& px, uint32_t slot) {
+    PixelHot hot;
+    hot.R = px.R;
+    hot.nv = px.nv;
+    hot.done = px.done;
+    store_hot(P.st, slot, hot);
+    P.st.rec[2u * slot + 1u] = L.sum;
+}
+// a query at its start as restart record k of the launch's yield queue (the next carry queue)
+__device__ __forceinline__ void coop_restart(const WaveParams& P, uint32_t k, const Ray& ray, float Pt, int pid, F4 pre,
+                                             uint32_t slot) {
+    Query q;
+    q_init_pre(ray, Pt, pid, pre, q);
+    uint32_t* w = P.yield_cq + (size_t)k * P.carry_words;
+    *reinterpret_cast<Query*>(w) = q;
+    w[sizeof(Query) / 4u] = slot;
+}
+// The wave's work counters (LDS, lane 0) to this XCD's statistics copy, and zeroed: each
+// to its total and to this engine's share (pt_stats coop_*; 0 = none).  The parameter
+// block is read here (karg), so the chain loop's wrap guard holds no register for it.
+__device__ __forceinline__ void lc_flush(uint32_t* lc) {
+    const WaveParams& K = karg<WaveParams>();
+    unsigned long long* ctr = ctr_copy(K.counters);
+    const bool grow = (K.side_flags & PT_STOP_GROW) != 0u;
+    const uint32_t total[LC_HANDED + 1u] = {0u, 1u, 2u, CTR_HO + (grow ? HO_GROW_YIELD : HO_SIDE_YIELD), 5u, 6u, CTR_HANDON};
+    const uint32_t share[LC_HANDED + 1u] = {8u, 9u, 10u, 0u, 13u, 0u, CTR_HO + (grow ? HO_GROW_HANDON : HO_SIDE_HANDON)};
+#pragma unroll
+    for (uint32_t k = 0; k <= LC_HANDED; ++k) {
+        const uint32_t v = lc[k];
+        if (!v) continue;
+        atomicAdd(ctr + total[k], (unsigned long long)v);
+        if (share[k]) atomicAdd(ctr + share[k], (unsigned long long)v);
+        // (every counted ray tests every plane)
+        if (k == LC_RAYS && K.S.n_planes) atomicAdd(ctr + 3, (unsigned long long)v * K.S.n_planes);
+        lc[k] = 0u;
+    }
 }
 
 #ifndef QC_WAVES_PER_EU
@@ -692,25 +732,8 @@ k_wcoop(WaveParams P) {
 #ifdef PT_CPROF
                     if (tl == 0u) cp[6]++;
 #endif
-                    if (gi < n_carry) {
-                        // a query suspended by the path engine: restarted from its ray (a query is a
-                        // function of the ray alone; its ray and plane tests were counted when taken)
-                        const uint32_t* w = P.cq[P.parity] + (size_t)gi * P.carry_words;
-                        ray = reinterpret_cast<const Query*>(w)->ray;
-                        slot = w[sizeof(Query) / 4u];
-                        q_planes_e(P.S, PlanesLds<BIG>{Q, P.S}, ray, Pt, pid);
-                        pre = q_prep(P.S, ray);
-                    } else {
-                        const uint32_t fi = gi - n_carry;
-                        const F4 o = FQ.ro[fi], d = FQ.rd[fi];
-                        ray.o = mk3(o.x, o.y, o.z);
-                        ray.d = mk3(d.x, d.y, d.z);
-                        slot = f2u(o.w);
-                        Pt = d.w;
-                        pid = FQ.pid[fi];
-                        pre = FQ.ri[fi];
-                        lc_add(lc, LC_RAYS, tl == 0u);
-                    }
+                    const bool fresh = coop_item<BIG>(P, Q, FQ, gi, n_carry, ray, slot, Pt, pid, pre);
+                    lc_add(lc, LC_RAYS, fresh && tl == 0u);
                     // the pixel's state for the chain's life: RNG / vertices / samples and the
                     // sum in the first lane's registers, the current path's fold records in LDS
                     const PixelHot hot = load_hot(P.st, slot);
@@ -780,14 +803,7 @@ k_wcoop(WaveParams P) {
             }
 #endif
             // the pixel has reached the pass target: its state back to HBM
-            if (tl == 0u) {
-                PixelHot hot;
-                hot.R = px.R;
-                hot.nv = px.nv;
-                hot.done = px.done;
-                store_hot(P.st, slot, hot);
-                P.st.rec[2u * slot + 1u] = L.sum;
-            }
+            if (tl == 0u) coop_store_pixel(P, L, px, slot);
             have = false;
         }
         if (__ballot(have) != 0ull) {
@@ -809,16 +825,7 @@ k_wcoop(WaveParams P) {
         }
         // (the wave's 32-bit visit counters go to the 64-bit statistics before they could wrap:
         // a chain cycle adds far less than 2^31)
-        if (lane == 0u && (lc[LC_NODES] | lc[LC_PTESTS] | lc[LC_AUX]) >= 0x80000000u) {
-            unsigned long long* ctr = ctr_copy(karg<WaveParams>().counters);
-            atomicAdd(ctr + 9, (unsigned long long)lc[LC_NODES]);
-            atomicAdd(ctr + 1, (unsigned long long)lc[LC_NODES]);
-            atomicAdd(ctr + 10, (unsigned long long)lc[LC_PTESTS]);
-            atomicAdd(ctr + 2, (unsigned long long)lc[LC_PTESTS]);
-            atomicAdd(ctr + 13, (unsigned long long)lc[LC_AUX]);
-            atomicAdd(ctr + 5, (unsigned long long)lc[LC_AUX]);
-            lc[LC_NODES] = lc[LC_PTESTS] = lc[LC_AUX] = 0u;
-        }
+        if (lane == 0u && (lc[LC_NODES] | lc[LC_PTESTS] | lc[LC_AUX]) >= 0x80000000u) lc_flush(lc);
         if (P.progress && prog >= 256u) {
             if (lane == 0u)
                 __hip_atomic_fetch_add(P.progress, (unsigned long long)prog, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -838,17 +845,8 @@ k_wcoop(WaveParams P) {
         // (k < carry_cap always: the host sizes the stops to the carry queue; a yield past it
         // would be a lost chain, which the resolve reports, never a write past the queue)
         if (have && tl == 0u && !drop && k < P.carry_cap) {
-            Query q;
-            q_init_pre(ray, Pt, pid, pre, q);
-            uint32_t* w = P.yield_cq + (size_t)k * P.carry_words;
-            *reinterpret_cast<Query*>(w) = q;
-            w[sizeof(Query) / 4u] = slot;
-            PixelHot hot;
-            hot.R = px.R;
-            hot.nv = px.nv;
-            hot.done = px.done;
-            store_hot(P.st, slot, hot);
-            P.st.rec[2u * slot + 1u] = L.sum;
+            coop_restart(P, k, ray, Pt, pid, pre, slot);
+            coop_store_pixel(P, L, px, slot);
         }
         const uint32_t nv = __shfl(px.nv, (int)tbase, 64);
         for (uint32_t v = tl; have && v < nv && (!BIG || v < QC_FOLD); v += T) P.st.fold[(size_t)slot * P.st.depth + v] = L.fold[v];
@@ -873,35 +871,14 @@ k_wcoop(WaveParams P) {
             int rid = -1;
             F4 rpre = F4{0.f, 0.f, 0.f, 0.f};
             uint32_t rslot = 0u;
-            if (on && gi < n_carry) {
-                const uint32_t* w = P.cq[P.parity] + (size_t)gi * P.carry_words;
-                r = reinterpret_cast<const Query*>(w)->ray;
-                rslot = w[sizeof(Query) / 4u];
-                q_planes_e(P.S, PlanesLds<BIG>{Q, P.S}, r, rp, rid);
-                rpre = q_prep(P.S, r);
-            } else if (on) {
-                const uint32_t fi = gi - n_carry;
-                const F4 o = FQ.ro[fi], d = FQ.rd[fi];
-                r.o = mk3(o.x, o.y, o.z);
-                r.d = mk3(d.x, d.y, d.z);
-                rslot = f2u(o.w);
-                rp = d.w;
-                rid = FQ.pid[fi];
-                rpre = FQ.ri[fi];
-            }
-            lc_add(lc, LC_RAYS, on && gi >= n_carry);
+            const bool fresh = on && coop_item<BIG>(P, Q, FQ, gi, n_carry, r, rslot, rp, rid, rpre);
+            lc_add(lc, LC_RAYS, fresh);
             lc_add(lc, LC_HANDED, on);
             // (hand-off site HO_SIDE_HANDON, or HO_GROW_HANDON; PT_TUNE drop=side_handon /
             // grow_handon: the items taken here are lost instead)
             const bool keep = on && P.drop != 1u + ((P.side_flags & PT_STOP_GROW) ? HO_GROW_HANDON : HO_SIDE_HANDON);
             const uint32_t k2 = wave_append(P.yield_ctr, keep);
-            if (keep && k2 < P.carry_cap) {
-                Query q;
-                q_init_pre(r, rp, rid, rpre, q);
-                uint32_t* w = P.yield_cq + (size_t)k2 * P.carry_words;
-                *reinterpret_cast<Query*>(w) = q;
-                w[sizeof(Query) / 4u] = rslot;
-            }
+            if (keep && k2 < P.carry_cap) coop_restart(P, k2, r, rp, rid, rpre, rslot);
         }
     }
     if (P.progress && lane == 0u && prog)
@@ -909,20 +886,7 @@ k_wcoop(WaveParams P) {
     // the wave's counters (LDS) to this XCD's statistics copy: the totals, and this engine's
     // share (pt_stats coop_*)
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (lane == 0u) {
-        unsigned long long* ctr = ctr_copy(P.counters);
-        const uint32_t v[LC_N] = {lc[0], lc[1], lc[2], lc[3], lc[4], lc[5], lc[6], lc[7]};
-        const bool grow = (P.side_flags & PT_STOP_GROW) != 0u;
-        const uint32_t to[LC_N] = {0u, 1u, 2u, CTR_HO + (grow ? HO_GROW_YIELD : HO_SIDE_YIELD), 5u, 6u, CTR_HANDON, 0u};
-        for (uint32_t k = 0; k < LC_HANDED + 1u; ++k)
-            if (v[k]) atomicAdd(ctr + to[k], (unsigned long long)v[k]);
-        if (v[LC_HANDED]) atomicAdd(ctr + CTR_HO + (grow ? HO_GROW_HANDON : HO_SIDE_HANDON), (unsigned long long)v[LC_HANDED]);
-        if (v[LC_RAYS] && P.S.n_planes) atomicAdd(ctr + 3, (unsigned long long)v[LC_RAYS] * P.S.n_planes);
-        if (v[LC_RAYS]) atomicAdd(ctr + 8, (unsigned long long)v[LC_RAYS]);
-        if (v[LC_NODES]) atomicAdd(ctr + 9, (unsigned long long)v[LC_NODES]);
-        if (v[LC_PTESTS]) atomicAdd(ctr + 10, (unsigned long long)v[LC_PTESTS]);
-        if (v[LC_AUX]) atomicAdd(ctr + 13, (unsigned long long)v[LC_AUX]);
-    }
+    if (lane == 0u) lc_flush(lc);
 #ifdef PT_CPROF
     // (per team first lanes: chain counts; cycle sums are per wave, counted by lane 0)
     cp[7] = __builtin_amdgcn_s_memtime() - cp_start;
@@ -946,8 +910,7 @@ hipError_t pt_preload_kernels_coop() {
 
 hipError_t pt_launch_coop(pt::WaveParams p, uint32_t grid, uint32_t team, bool big, hipStream_t s, hipEvent_t e0,
                           hipEvent_t e1) {
-    hipError_t e = hipMemsetAsync(p.ctl + PT_CTL_SET * (1u - p.parity), 0, 4u * PT_CTL_SET, s);
-    if (e != hipSuccess) return e;
+    hipError_t e;
     p.path = 1u;
     if (e0 && (e = hipEventRecord(e0, s)) != hipSuccess) return e;
     if (big) {

@@ -136,6 +136,7 @@ uint64_t owned_pixels(const pt_session* ss);
 hipError_t read_counters(pt_session* ss, unsigned long long c[PT_CTR_STRIDE]);
 int flush_trace(pt_session* ss);
 int trace_wave(pt_session* ss, uint32_t spp);
+pt::SceneView device_view(const pt_session* ss);
 // the hand-off site named `name` (PT_HO_*: "suspend", "flush", "ringout", "exact", "side_take",
 // "side_yield", "side_handon", "grow_yield", "grow_handon"), or -1
 int handoff_site(const char* name);
@@ -247,8 +248,12 @@ struct pt_session {
     unsigned long long roundlog_rays = 0;
     uint32_t shade_grid = 0, rounds = 0;
     hipStream_t stream = nullptr;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending, pending_isect;
-    std::vector<bool> pending_isect_coop;   // which of pending_isect are cooperative-engine launches
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;   // the passes' event pairs (kernel_ms)
+    struct LaunchEvents {
+        hipEvent_t e0, e1;
+        bool coop;                // a cooperative-engine launch (coop_ms)
+    };
+    std::vector<LaunchEvents> pending_isect;   // the rounds' launches (isect_ms)
     double kernel_ms = 0.0, resolve_ms = 0.0, isect_ms = 0.0, coop_ms = 0.0;
     uint64_t isect_launches = 0, coop_launches = 0;
     uint64_t samples_done = 0;

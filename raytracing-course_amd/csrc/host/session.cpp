@@ -25,20 +25,20 @@ int finish_pending(pt_session* ss) {
     // diagnostics (PT_TUNE roundlog=1): per-launch ms of the rounds, one line per sync
     const bool log = tune_int("roundlog", 0) == 1 && !ss->pending_isect.empty();
     if (log) fprintf(stderr, "rounds_ms");
-    for (size_t i = 0; i < ss->pending_isect.size(); ++i) {
-        const auto& e = ss->pending_isect[i];
+    for (const auto& e : ss->pending_isect) {
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, e.first, e.second) == hipSuccess) {
+        if (hipEventElapsedTime(&ms, e.e0, e.e1) == hipSuccess) {
             ss->isect_ms += ms;
-            if (i < ss->pending_isect_coop.size() && ss->pending_isect_coop[i]) ss->coop_ms += ms;
+            if (e.coop) ss->coop_ms += ms;
         }
         if (log) fprintf(stderr, " %.3f", ms);
-        (void)hipEventDestroy(e.first);
-        (void)hipEventDestroy(e.second);
+        (void)hipEventDestroy(e.e0);
+        (void)hipEventDestroy(e.e1);
     }
     if (log) fprintf(stderr, "\n");
     ss->pending_isect.clear();
-    ss->pending_isect_coop.clear();
+    // (a pass that failed midway leaves pairs without an end: not an error of the next launch)
+    (void)hipGetLastError();
     return PT_OK;
 }
 
@@ -82,6 +82,28 @@ int flush_trace(pt_session* ss) {
     ss->deferred_spp = 0;
     HIP_TRY(hipSetDevice(ss->dev));
     return trace_wave(ss, spp);
+}
+
+// the scene's copy on the session's device as the kernels see it (without the megakernel's aux BVH)
+pt::SceneView device_view(const pt_session* ss) {
+    const DevScene& ds = *ss->ds;
+    const pt_scene* s = ss->sc;
+    pt::SceneView v;
+    memset(&v, 0, sizeof(v));
+    v.nodes = ds.nodes;
+    v.prims = ds.prims;
+    v.shade = ds.shade;
+    v.planes = ds.planes;
+    v.emitters = ds.emitters;
+    v.n_planes = (uint32_t)s->planes.size();
+    v.n_emitters = (uint32_t)s->emitters.size();
+    v.inv_emitters = s->emitters.empty() ? 0.f : 1.f / (float)s->emitters.size();
+    v.bg = pt::mk3(s->hs.bg[0], s->hs.bg[1], s->hs.bg[2]);
+    v.box_extent = s->box_extent;
+    v.anc_info = ds.anc_info;
+    v.anc = ds.anc;
+    set_blob(v, s, ds.blob);
+    return v;
 }
 
 bool coop_big(const pt_session* ss) {
@@ -434,20 +456,9 @@ int pt_session_trace(pt_session* ss, uint32_t spp) {
     const DevScene& ds = *ss->ds;
     pt::TraceParams tp;
     const pt_scene* s = ss->sc;
+    tp.S = device_view(ss);
     tp.S.aux = ss->traversal == PT_TRAVERSAL_EXACT ? nullptr : ds.aux;
     tp.cfg = replay_cfg(s);
-    tp.S.nodes = ds.nodes;
-    tp.S.prims = ds.prims;
-    tp.S.shade = ds.shade;
-    tp.S.planes = ds.planes;
-    tp.S.emitters = ds.emitters;
-    tp.S.n_planes = (uint32_t)s->planes.size();
-    tp.S.n_emitters = (uint32_t)s->emitters.size();
-    tp.S.inv_emitters = s->emitters.empty() ? 0.f : 1.f / (float)s->emitters.size();
-    tp.S.bg = pt::mk3(s->hs.bg[0], s->hs.bg[1], s->hs.bg[2]);
-    tp.S.box_extent = s->box_extent;
-    tp.S.anc_info = ds.anc_info;
-    tp.S.anc = ds.anc;
     tp.cam = ss->cam;
     tp.tm = ss->tm;
     tp.st = ss->st;

@@ -341,10 +341,16 @@ def test_render_gather_paths(pt, ngpu_gather):
     assert r.view(np.uint32).tolist() == rad.view(np.uint32).tolist()
 
 
-def test_session_reset_renders_the_job_again(pt):
+@pytest.mark.parametrize("tune", ["", "coop=0,budget=2", "coop=300,budget=2,early=1,early_at=100000000"],
+                         ids=["default", "path_rounds", "side_launch"])
+def test_session_reset_renders_the_job_again(pt, tune, monkeypatch):
     """pt_session_reset restarts every owned pixel at sample 0: after any pass, reset +
     trace(S) gives the bytes, radiance and rays of a new session's trace(S) (bench.py
-    repeats the metric's frame this way)."""
+    repeats the metric's frame this way).  The default runs this scene's whole pass on the
+    cooperative engine; the PT_TUNE cases (read at session creation) re-enter the pass loop
+    on one session through the path rounds, and through the early launch on the side
+    stream, as a 1080p frame does."""
+    monkeypatch.setenv("PT_TUNE", tune)
     m, img, rad = U.golden_image("dragon_64x64x16")
     with pt.Scene.load(U.golden_scene_path("dragon_64x64x16")) as s:
         s.prepare()
