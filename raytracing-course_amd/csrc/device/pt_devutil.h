@@ -84,14 +84,57 @@ __device__ __forceinline__ f3 load_sum(const PixelState& st, uint32_t slot) {
     const uint4 v = st.rec[2u * slot + 1u];
     return mk3(u2f(v.x), u2f(v.y), u2f(v.z));
 }
-// the sum and the slot's global pixel index (one 16-B load)
-__device__ __forceinline__ f3 load_sum_pix(const PixelState& st, uint32_t slot, uint32_t& pix) {
-    const uint4 v = st.rec[2u * slot + 1u];
-    pix = v.w;
-    return mk3(u2f(v.x), u2f(v.y), u2f(v.z));
-}
 __device__ __forceinline__ void store_sum(const PixelState& st, uint32_t slot, f3 s, uint32_t pix) {
     st.rec[2u * slot + 1u] = make_uint4(f2u(s.x), f2u(s.y), f2u(s.z), pix);
+}
+
+// vertices per chunk of fold_path (>= the bench job's RAY_DEPTH 6: one chunk there)
+#ifndef PT_FOLD_CH
+#define PT_FOLD_CH 6u
+#endif
+// Loaded values the optimiser must have in registers at this point: the loads before it are
+// neither sunk into the branches that use them nor issued one by one between their uses
+__device__ __forceinline__ void landed(uint32_t& a, uint32_t& b, uint32_t& c) {
+    asm volatile("" : "+v"(a), "+v"(b), "+v"(c));
+}
+__device__ __forceinline__ void landed(float& a, float& b, float& c) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c)); }
+// An ended path's backward fold into its pixel's sum (src/scene.cpp:198): returns
+// sum + fold(L) for the slot's nv fold records, deepest first, with `L` the leaf value,
+// and the slot's global pixel index in `pix`.  The loads go out in batches, not as a
+// chain of round trips (a record, then the shading record it names, vertex by vertex,
+// then the sum): per chunk of PT_FOLD_CH vertices every fold record together (with the
+// sum in the first chunk), one wait, every shading record together, one wait, then the
+// arithmetic in registers -- 3 round trips for a path of up to PT_FOLD_CH vertices
+// instead of 2 nv + 1.  A position past the path's start loads record 0 of the slot and
+// shading record 0 instead of branching (unconditional repeated loads: see q_step), and
+// folds nothing; its prim index is NOT taken from the loaded record, which is whatever
+// the slot's fold area held (uninitialised before the slot's first vertex).  Shading
+// record 0 can always be read: the scene blob goes on behind the table (scene_api.cpp).
+__device__ __forceinline__ f3 fold_path(const PixelState& st, const Shade* shade, uint32_t slot, uint32_t nv, f3 L,
+                                        uint32_t& pix) {
+    const uint4* rec = st.fold + (size_t)slot * st.depth;
+    const uint4 sp = st.rec[2u * slot + 1u];
+    for (uint32_t top = nv;; top -= PT_FOLD_CH) {   // this chunk: vertices top-1 down to top-PT_FOLD_CH
+        uint4 r[PT_FOLD_CH];
+#pragma unroll
+        for (uint32_t j = 0; j < PT_FOLD_CH; ++j) r[j] = rec[j < top ? top - 1u - j : 0u];
+#pragma unroll
+        for (uint32_t j = 0; j < PT_FOLD_CH; ++j) landed(r[j].x, r[j].y, r[j].z);
+        Shade sh[PT_FOLD_CH];
+#pragma unroll
+        for (uint32_t j = 0; j < PT_FOLD_CH; ++j) sh[j] = shade[j < top ? r[j].x & 0x3fffffffu : 0u];
+#pragma unroll
+        for (uint32_t j = 0; j < PT_FOLD_CH; ++j) {
+            landed(sh[j].s0.x, sh[j].s0.y, sh[j].s0.z);
+            landed(sh[j].s1.x, sh[j].s1.y, sh[j].s1.z);
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < PT_FOLD_CH; ++j)
+            if (j < top) L = fold_vertex_sh(sh[j], L, r[j].x, u2f(r[j].y), u2f(r[j].z));
+        if (top <= PT_FOLD_CH) break;
+    }
+    pix = sp.w;
+    return mk3(u2f(sp.x), u2f(sp.y), u2f(sp.z)) + L;   // src/scene.cpp:198 sum += RayTrace(...)
 }
 
 // owned slot -> global pixel (16x16 tiles of the window, dealt to ranks by tile_owner)

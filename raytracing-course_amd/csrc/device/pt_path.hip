@@ -59,17 +59,9 @@ __device__ __forceinline__ bool end_item(const WaveParams& P, uint4* H, uint32_t
                                          Ray& ray) {
     PixelHot hot = hot_unpack(lds_get(H, cid));
     Rng R = hot.R;
-    f3 L = miss ? P.S.bg : mk3(0.f, 0.f, 0.f);
-    HbmVStore vs = fold_store(P.st, slot);
-    for (uint32_t k = hot.nv; k > 0u; --k) {
-        uint32_t idm;
-        float s1, s2;
-        vs.get(k - 1u, idm, s1, s2);
-        L = fold_vertex(P.S, L, idm, s1, s2);
-    }
     uint32_t pix;
-    const f3 sum = load_sum_pix(P.st, slot, pix);
-    store_sum(P.st, slot, sum + L, pix);
+    const f3 sum = fold_path(P.st, P.S.shade, slot, hot.nv, miss ? P.S.bg : mk3(0.f, 0.f, 0.f), pix);
+    store_sum(P.st, slot, sum, pix);
     hot.done += 1u;
     hot.nv = 0u;
     bool emit = false;
@@ -537,13 +529,16 @@ __device__ __forceinline__ void path_shade_wave(const WaveParams& P, PathLds& L)
             // a batch of ended paths: folds, sums, the next samples' camera rays
             const uint32_t n = pend < 64u ? pend : 64u;
             have = lane < n;
+            uint2 v = make_uint2(0u, 0u);
+            if (have) v = endq[(e_head + lane) % PT_CMAX];
+            pf.end_read(n, v.x);
             if (have) {
-                const uint2 v = endq[(e_head + lane) % PT_CMAX];
                 slot = v.x & 0x7fffffffu;
                 cid = v.y;
                 emit = end_item(P, L.H, cid, slot, (v.x >> 31) != 0u, ray);
                 sdone = true;
             }
+            pf.end_done(emit ? f2u(ray.d.x) : 0u);
             e_head += n;
         } else if (total == 0u) {
             if (lds_read(L.qw_done) == PT_NQ) {

@@ -117,17 +117,9 @@ __device__ __forceinline__ bool shade_item(const WaveParams& P, const EM& em, ui
     sdone = end != PE_LIVE;
     if (end != PE_LIVE) {
         // path over: backward fold (deepest vertex first), src/scene.cpp:198 sum += ...
-        f3 L = end == PE_MISS ? P.S.bg : mk3(0.f, 0.f, 0.f);
-        HbmVStore vs = fold_store(P.st, slot);
-        for (uint32_t k = nv; k > 0u; --k) {
-            uint32_t idm;
-            float s1, s2;
-            vs.get(k - 1u, idm, s1, s2);
-            L = fold_vertex(P.S, L, idm, s1, s2);
-        }
         uint32_t pix;
-        const f3 sum = load_sum_pix(P.st, slot, pix);
-        store_sum(P.st, slot, sum + L, pix);   // src/scene.cpp:198 sum += RayTrace(...)
+        const f3 sum = fold_path(P.st, P.S.shade, slot, nv, end == PE_MISS ? P.S.bg : mk3(0.f, 0.f, 0.f), pix);
+        store_sum(P.st, slot, sum, pix);
         const uint32_t done = hot.done + 1u;
         hot.done = done;
         nv = 0u;

@@ -109,6 +109,7 @@ struct QProf {
 };
 struct SProf {
     uint64_t batches = 0, items = 0, spin_ = 0, cyc = 0, shc = 0, pushc = 0, c0 = 0, c1 = 0, c2 = 0;
+    uint64_t ebatches = 0, eitems = 0, endc = 0;   // batches of ended paths (folds): counted apart
     __device__ void begin() { c0 = c2 = __builtin_amdgcn_s_memtime(); }
     __device__ void spin() { spin_++; }
     __device__ void batch(uint32_t n) {
@@ -120,6 +121,20 @@ struct SProf {
     __device__ void shaded() {
         c2 = __builtin_amdgcn_s_memtime();
         shc += c2 - c1;
+    }
+    // a batch of n ended paths, its endq entries read (`dep`: a loaded word, so the clock is
+    // read after the load has returned) ...
+    __device__ void end_read(uint32_t n, uint32_t dep) {
+        asm volatile("" ::"v"(dep));
+        c1 = __builtin_amdgcn_s_memtime();
+        ebatches++;
+        eitems += n;
+    }
+    // ... and its end_item calls done (`dep`: a word of their result); what follows is the push
+    __device__ void end_done(uint32_t dep) {
+        asm volatile("" ::"v"(dep));
+        c2 = __builtin_amdgcn_s_memtime();
+        endc += c2 - c1;
     }
     __device__ void end() {
         const uint64_t c3 = __builtin_amdgcn_s_memtime();
@@ -135,6 +150,9 @@ struct SProf {
         w[10] = cyc;
         w[27] = shc;
         w[28] = pushc;
+        w[29] = ebatches;
+        w[30] = eitems;
+        w[31] = endc;
         w[1] = __builtin_amdgcn_s_memrealtime();
     }
 };
@@ -165,6 +183,8 @@ struct SProf {
     __device__ void batch(uint32_t) {}
     __device__ void read_done() {}
     __device__ void shaded() {}
+    __device__ void end_read(uint32_t, uint32_t) {}
+    __device__ void end_done(uint32_t) {}
     __device__ void end() {}
     __device__ void store(unsigned long long*) const {}
 };

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Summarise a PT_TUNE wgprof dump of the path engine (-DPT_WPROF build): 64 u64 per
 workgroup per round: start, end (100 MHz), QW trips, QW active lane-trips, QW
-sleep trips, ring takes, rays, SW batches, SW items, SW spins, SW busy cycles."""
+sleep trips, ring takes, rays, SW batches, SW items, SW spins, SW busy cycles, ...;
+words 29-31: the SW's batches of ended paths (count, items, cycles)."""
 import sys
 import numpy as np
 
@@ -32,6 +33,11 @@ print("QW cycles per trip: refill %.0f, step %.0f, done %.0f; trips with aux lan
          tot[24] / max(tot[2], 1), tot[25] / max(tot[2], 1)))
 print("SW cycles per batch: shade_item %.0f, next-ray push + publish %.0f, the rest (ring reads, fences) %.0f"
       % (tot[27] / max(tot[7], 1), tot[28] / max(tot[7], 1), (tot[10] - tot[27] - tot[28]) / max(tot[7], 1)))
+# batches of ended paths (the folds): timed from after the endq read to after the end_item
+# calls, apart from the vertex batches' push time (their share of the SW's busy cycles last)
+print("SW end batches: %d, items/batch %.1f, cycles/batch %.0f (%.3f of SW busy cycles; one per %.1f vertex batches)"
+      % (tot[29], tot[30] / max(tot[29], 1), tot[31] / max(tot[29], 1), tot[31] / max(tot[10], 1),
+         tot[7] / max(tot[29], 1)))
 print("QW step: load wait %.0f + exec %.0f cycles per stepping trip; refill data wait %.0f cycles per refilling trip (%.3f of trips)"
       % (tot[32] / max(tot[2] - tot[4], 1), tot[33] / max(tot[2] - tot[4], 1), tot[34] / max(tot[35], 1), tot[35] / max(tot[2], 1)))
 print("SW per batch: ring read wait %.0f; shade_item phases: pixel+prim %.0f, vertex %.0f, fold+sum %.0f, next ray+store %.0f"
