@@ -107,7 +107,7 @@ struct WaveParams {
     uint32_t carry_cap, carry_words;
     DoneQ done;
     RayQ ex;                      // rays handed to the exact DFS this round
-    uint2* endq;                  // per path workgroup PT_CMAX entries: its shade wave's ended paths
+    uint2* endq;                  // per path workgroup path_cmax(NQ) entries: its shade wave's ended paths
                                   // {slot | miss << 31, LDS pixel-table entry}
     uint32_t* ctl;                // 2 x PT_CTL_SET round counters
     unsigned long long* counters; // rays, nodes, prim tests, plane tests, errors, aux visits, fallbacks, ray fallbacks
@@ -125,7 +125,7 @@ struct WaveParams {
                                   // every wave of the round stops at that one time
     uint32_t path_runend;         // a round with at most this many chains runs them to the end of the pass
     unsigned long long* progress; // optional host-mapped count of finished samples (progress bar), or null
-    uint32_t path_cap;            // chains a workgroup may hold (<= PT_CMAX)
+    uint32_t path_cap;            // chains a workgroup may hold (<= path_cmax(NQ))
     uint32_t lstack;              // aux stack words a query lane may use (<= PT_LSTACK; deeper: exact DFS)
     const uint32_t* tile_order;   // k_wcamera: block b seeds local tile tile_order[b] (null: tile b)
     uint32_t sparse_steps;        // steps per loop trip of the end-of-pass (sparse) kernel
@@ -180,15 +180,22 @@ struct WaveParams {
 #define PT_SHADE_HOLD 32u
 #define PT_ORDER_BUCKETS 256u
 
-// path engine geometry: PT_NQ query waves + 1 shade wave per workgroup; at most
-// PT_CMAX chains resident per workgroup (= the capacity of its ray ring).
+// path engine geometry: NQ query waves + 1 shade wave per workgroup (a template
+// parameter of the engine: k_wpath<NQ, SPARSE>); at most path_cmax(NQ) chains resident
+// per workgroup (= the capacity of its ray ring).
 // Two query waves per shade wave since the hit-region query made the queries
 // cheaper than their shading (3 -> 2 at 4 workgroups per CU: +13 % at rank-of-1,
-// +20 % at rank-of-8; 1 query wave: -8 %)
-#ifndef PT_NQ
-#define PT_NQ 2u
+// +20 % at rank-of-8; 1 query wave: -8 %).  The low-chain rounds, the end-of-pass
+// kernel and everything beside a cooperative launch run that shape; the full rounds may
+// run NQ = 3 at 3 workgroups per CU (PT_TUNE nq): 9 query waves per CU
+// against 8, at the same 3 waves per SIMD.  Measured again in round 8 (profiles/r08_nq3):
+// -12 % on the bench (a rank of 1), -13 % to -18 % at rank 0 of 8 -- at the product's rate the shade wave already takes 48 items
+// per batch with 2 query waves, and with 3 its batches are full (60 of 64) and the done
+// rings fill (36 of 48): the shade wave sets the rate.  2 stays the default.
+#define PT_NQ_BASE 2u
+#ifndef PT_NQ_FULL
+#define PT_NQ_FULL 2u                  // the full rounds' shape when PT_TUNE nq is not given
 #endif
-#define PT_PATH_WG (64u * (PT_NQ + 1u))
 #ifndef PT_PATH_WAVES_PER_EU
 #define PT_PATH_WAVES_PER_EU 3u        // k_wpath occupancy (waves per SIMD) the compiler is held to
 #endif
@@ -213,11 +220,18 @@ struct WaveParams {
 #ifndef PT_CMAX
 #define PT_CMAX 384u                   // (512 until round 3; the LDS pixel table took the room)
 #endif
+#ifndef PT_CMAX3
+#define PT_CMAX3 384u                  // ... of an NQ = 3 workgroup (448 measured the same; 480 = 53,840 B ran only 2
+                                       // workgroups per CU: LDS is allocated in coarser steps than a byte)
+#endif
+// a shape's chain capacity and its workgroups per CU (PT_PATH_WAVES_PER_EU waves on each of 4 SIMDs)
+constexpr uint32_t path_cmax(uint32_t nq) { return nq == 3u ? PT_CMAX3 : PT_CMAX; }
+constexpr uint32_t path_wg_per_cu(uint32_t nq) { return PT_PATH_WAVES_PER_EU * 4u / (nq + 1u); }
 // The rings, the query lanes' aux stacks and the resident chains' pixel records
-// live in LDS (4 workgroups per CU; pt_path.hip static_asserts the fit):
-//   pixel table PT_CMAX entries (16 B: RNG, vertex count, samples done -- rec[2 slot]
+// live in LDS (4 workgroups of NQ = 2 per CU, or 3 of NQ = 3; pt_path.hip static_asserts the fit):
+//   pixel table path_cmax(NQ) entries (16 B: RNG, vertex count, samples done -- rec[2 slot]
 //              while the chain stays in the workgroup) and their free ring
-//   ray ring   PT_CMAX entries (54 B: ray, slot, plane t and prim, q_prep record, table entry)
+//   ray ring   path_cmax(NQ) entries (54 B: ray, slot, plane t and prim, q_prep record, table entry)
 //   done rings PT_DQN entries per query wave (34 B: ray, slot, closest prim, table entry),
 //              flow-controlled (a finished query waits in its lane while its ring is full)
 //   aux stack  PT_LSTACK words per query lane; a query that would need more takes the
@@ -274,8 +288,10 @@ hipError_t pt_launch_wave_start(pt::WaveParams p, hipStream_t s);
 // sparse: the end-of-pass kernel (few chains: every step kind and several steps per trip)
 // (neither this nor pt_launch_coop zeroes the round's output counter set: the pass loop does,
 // once per round -- host/rounds.cpp zero_round_out)
-hipError_t pt_launch_path_round(pt::WaveParams p, uint32_t path_grid, uint32_t shade_grid, hipStream_t s, bool sparse,
-                                hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// nq: the launch's shape, query waves per workgroup (2, or 3 -- not the sparse kernel); p.endq holds
+// path_cmax(nq) entries per workgroup and p.path_cap is at most path_cmax(nq)
+hipError_t pt_launch_path_round(pt::WaveParams p, uint32_t nq, uint32_t path_grid, uint32_t shade_grid, hipStream_t s,
+                                bool sparse, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 // the cooperative engine's intake order (WaveParams::order): the round's n work items
 // counting-sorted by their pixels' remaining samples, most first
 hipError_t pt_launch_coop_order(pt::WaveParams p, uint32_t n, hipStream_t s);

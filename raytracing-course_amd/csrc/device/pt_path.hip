@@ -1,13 +1,13 @@
 // pt_path.hip -- the path engine k_wpath: persistent, warp-specialised
-// workgroups of PT_NQ query waves and one shade wave; a pixel's chain keeps going
+// workgroups of NQ query waves and one shade wave; a pixel's chain keeps going
 // inside the kernel through LDS rings.  pt_wave.h has the pass's outline.
 #include "pt_wave.h"
 
 namespace pt {
 
 // ---- path engine -------------------------------------------------------------
-// k_wpath: persistent and warp-specialised.  A workgroup is PT_NQ query waves
-// plus one shade wave.  A pixel's chain (its one ray in flight) is always in
+// k_wpath: persistent and warp-specialised.  A workgroup is NQ query waves
+// plus one shade wave (NQ = 2, or 3 in the full rounds: pt_kernels.h path_cmax).  A pixel's chain (its one ray in flight) is always in
 // exactly one place: a query lane, the done ring (query finished, waiting to be
 // shaded), a shade lane, or the ray ring (its next ray, waiting for a query
 // lane).  Query lanes refill from the ray ring first and from the round's work
@@ -80,49 +80,62 @@ __device__ __forceinline__ bool end_item(const WaveParams& P, uint4* H, uint32_t
 // Rings: entries and positions in LDS, ordered by workgroup-scope release/acquire
 // fences.  Every ring has ONE producer, which publishes its entries in order, so a
 // consumer takes a contiguous range: the ray ring is written by the shade wave, and
-// each query wave has its own done ring.  At most PT_CMAX chains are resident per
-// workgroup and a chain has at most one ring entry, so the ray ring (PT_CMAX
+// each query wave has its own done ring.  At most CMAX chains are resident per
+// workgroup and a chain has at most one ring entry, so the ray ring (CMAX
 // entries) never overflows; a done ring (PT_DQN entries) is flow-controlled by its
 // consumer's head.  No entry is overwritten before it has been read.
+template <uint32_t NQ>
 struct PathLds {
+    static constexpr uint32_t CMAX = path_cmax(NQ);   // chains a workgroup of this shape holds at most
     uint32_t rq_head;             // next ray-ring entry to take (query waves, CAS)
     uint32_t rq_tail;             // ray-ring entries published (shade wave)
     uint32_t resident;            // chains held by this workgroup
     uint32_t leaked;              // chains handed to the exact DFS (their table entries stay taken)
     uint32_t qw_done;             // query waves that have left
     uint32_t f_head;              // pixel-table entries taken from the free ring (query waves, atomic)
-    uint32_t dq_tail[PT_NQ];      // done-ring entries published, per query wave
-    uint32_t dq_head[PT_NQ];      // done-ring entries read by the shade wave (free space for the producer)
+    uint32_t dq_tail[NQ];      // done-ring entries published, per query wave
+    uint32_t dq_head[NQ];      // done-ring entries read by the shade wave (free space for the producer)
     // The resident chains' pixel records (rec[2 slot]: RNG, vertex count, samples
     // done): a chain takes an entry when it joins the workgroup (query wave intake)
     // and its record lives here, not in HBM, until it leaves -- its pixel reaches the
     // pass target (the shade wave writes it back and frees the entry), or the round
     // ends or the exact DFS takes its ray (written back, the entry stays taken).
-    uint4 H[PT_CMAX];
-    uint16_t F[PT_CMAX];          // free entries (ring: taken at f_head, returned by the shade wave)
-    F4 rq_ro[PT_CMAX];            // ray ring: {o.xyz, slot}
-    F4 rq_rd[PT_CMAX];            //           {d.xyz, P}
-    F4 rq_ri[PT_CMAX];            //           q_prep record
-    int rq_pid[PT_CMAX];          //           closest plane
-    uint16_t rq_cid[PT_CMAX];     //           pixel-table entry
-    F4 dq_ro[PT_NQ][PT_DQN];      // done rings: {o.xyz, slot}
-    F4 dq_rd[PT_NQ][PT_DQN];      //             {d.xyz, u32 closest prim | 0xffffffff}
-    uint16_t dq_cid[PT_NQ][PT_DQN];   //         pixel-table entry
-    uint32_t stk[(PT_LSTACK + 1u) * 64u * PT_NQ];   // query lanes' aux stacks, [word][lane] (+ a trash word)
+    uint4 H[CMAX];
+    uint16_t F[CMAX];          // free entries (ring: taken at f_head, returned by the shade wave)
+    F4 rq_ro[CMAX];            // ray ring: {o.xyz, slot}
+    F4 rq_rd[CMAX];            //           {d.xyz, P}
+    F4 rq_ri[CMAX];            //           q_prep record
+    int rq_pid[CMAX];          //           closest plane
+    uint16_t rq_cid[CMAX];     //           pixel-table entry
+    F4 dq_ro[NQ][PT_DQN];      // done rings: {o.xyz, slot}
+    F4 dq_rd[NQ][PT_DQN];      //             {d.xyz, u32 closest prim | 0xffffffff}
+    uint16_t dq_cid[NQ][PT_DQN];   //         pixel-table entry
+    uint32_t stk[(PT_LSTACK + 1u) * 64u * NQ];   // query lanes' aux stacks, [word][lane] (+ a trash word)
     // the shade wave's copies of the first planes and emitters (any further ones: HBM);
     // a plane's record carries its prim index in p2.w (unused by a plane)
     F4 pl[QC_NPL * 5u];
     F4 em[QC_NEM * 5u];
 };
-static_assert(PT_CMAX <= 1024u, "Query::cid is a 10-bit field");
 // k_wpath's occupancy (PT_PATH_WAVES_PER_EU waves per SIMD, 4 SIMDs per CU) assumes
-// that many workgroups fit the CU's 160 KB of LDS: a bigger ring, stack or table
-// would silently drop a workgroup per CU (every tuning number assumes 4)
-static_assert((PT_PATH_WAVES_PER_EU * 4u / (PT_NQ + 1u)) * sizeof(PathLds) <= 160u * 1024u,
-              "PathLds no longer fits PT_PATH_WAVES_PER_EU*4/(PT_NQ+1) workgroups per CU");
+// that path_wg_per_cu(NQ) workgroups fit the CU's 160 KB of LDS: a bigger ring, stack or
+// table would silently drop a workgroup per CU (every tuning number assumes 4 of NQ = 2,
+// 3 of NQ = 3)
+template <uint32_t NQ>
+constexpr bool path_lds_fits() {
+    static_assert(PathLds<NQ>::CMAX <= 1024u, "Query::cid is a 10-bit field");
+    // (a workgroup's LDS is allocated in steps: 3 x 53,840 B, under 160 KB by the byte, ran 2 per CU and
+    // 3 x 51,536 B ran 3; the step is not documented, 2 KB is assumed here)
+    static_assert(path_wg_per_cu(NQ) * ((sizeof(PathLds<NQ>) + 2047u) & ~(size_t)2047u) <= 160u * 1024u,
+                  "PathLds<NQ> no longer fits path_wg_per_cu(NQ) workgroups per CU");
+    return true;
+}
+static_assert(path_lds_fits<2u>() && path_lds_fits<3u>(), "");
+// (the low-chain rounds run 2 workgroups of NQ = 2 per CU beside a k_wcoop<4> workgroup's 70,176 B)
+static_assert(sizeof(PathLds<2u>) == 40944u, "PathLds<2>: the size the low-chain rounds' occupancy was measured at");
 // the first QC_NPL planes / QC_NEM emitters from the workgroup's LDS copy, any further ones from HBM
+template <class LL>
 struct PlanesPath {
-    const PathLds& L;
+    const LL& L;
     const SceneView& S;
     __device__ Prim operator()(uint32_t k, uint32_t& pi) const {
         if (k < QC_NPL) {
@@ -137,8 +150,9 @@ struct PlanesPath {
         return S.prims[pi];
     }
 };
+template <class LL>
 struct EmitPath {
-    const PathLds& L;
+    const LL& L;
     const SceneView& S;
     __device__ Prim operator()(uint32_t k) const {
         if (k < QC_NEM) {
@@ -164,14 +178,15 @@ struct EmitPath {
 // bound by each chain's latency, not by issue): a trip runs every step kind and
 // up to P.sparse_steps steps.  A separate instantiation, so its registers do not
 // weigh on the main kernel.
-template <bool SPARSE>
-__device__ __forceinline__ void path_query_wave(const WaveParams& P, PathLds& L, uint32_t qw) {
-    LdsMemN<64u * PT_NQ> stk{L.stk + 64u * qw + lane_id(), P.lstack, PT_LSTACK};
+template <uint32_t NQ, bool SPARSE>
+__device__ __forceinline__ void path_query_wave(const WaveParams& P, PathLds<NQ>& L, uint32_t qw) {
+    constexpr uint32_t CMAX = PathLds<NQ>::CMAX;
+    LdsMemN<64u * NQ> stk{L.stk + 64u * qw + lane_id(), P.lstack, PT_LSTACK};
     const uint32_t p = P.parity;
     const uint32_t* in = P.ctl + PT_CTL_SET * p;
     uint32_t* out = P.ctl + PT_CTL_SET * (1u - p);
     const uint32_t n_carry = in[C_CARRY], n_total = P.pin ? P.pin_n : in[C_FRESH] + n_carry;
-    const uint32_t n_waves = gridDim.x * PT_NQ;
+    const uint32_t n_waves = gridDim.x * NQ;
     // Rounds exist to rebalance chains between workgroups.  Once the round's chains
     // fit in the query lanes (the tail of a pass: only the slowest pixels are left)
     // suspending gains nothing and costs a round: run them to the end.
@@ -287,7 +302,7 @@ __device__ __forceinline__ void path_query_wave(const WaveParams& P, PathLds& L,
                 }
                 h = __builtin_amdgcn_readfirstlane(h);
                 take = __builtin_amdgcn_readfirstlane(take);
-                if (!active && pos >= given && pos < given + take) { src = 2u; gi = (h + pos - given) % PT_CMAX; }
+                if (!active && pos >= given && pos < given + take) { src = 2u; gi = (h + pos - given) % CMAX; }
                 given += take;
                 pf.ring(take);
             }
@@ -328,7 +343,7 @@ __device__ __forceinline__ void path_query_wave(const WaveParams& P, PathLds& L,
             }
             // chains joining the workgroup (src 1: the round's work) take a pixel-table
             // entry from the free ring (there are enough: the entries taken never exceed
-            // resident + leaked <= path_cap <= PT_CMAX); ray-ring chains bring theirs
+            // resident + leaked <= path_cap <= CMAX); ray-ring chains bring theirs
             const unsigned long long mjoin = __ballot(src == 1u);
             uint32_t fh = 0u;
             if (mjoin) {
@@ -337,7 +352,7 @@ __device__ __forceinline__ void path_query_wave(const WaveParams& P, PathLds& L,
             }
             if (src != 0u) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             uint32_t cid = 0u;
-            if (src == 1u) cid = lds_get(L.F, (fh + lanes_below(mjoin)) % PT_CMAX);
+            if (src == 1u) cid = lds_get(L.F, (fh + lanes_below(mjoin)) % CMAX);
             if (src == 2u) cid = lds_get(L.rq_cid, gi);
             if (src == 1u) {
                 const uint32_t* pin = karg<WaveParams>().pin;
@@ -490,19 +505,21 @@ __device__ __forceinline__ void path_query_wave(const WaveParams& P, PathLds& L,
     if (lane_id() == 0u) atomicAdd(&L.qw_done, 1u);
 }
 
-__device__ __forceinline__ void path_shade_wave(const WaveParams& P, PathLds& L) {
+template <uint32_t NQ>
+__device__ __forceinline__ void path_shade_wave(const WaveParams& P, PathLds<NQ>& L) {
+    constexpr uint32_t CMAX = PathLds<NQ>::CMAX;
     uint32_t* out = P.ctl + PT_CTL_SET * (1u - P.parity);
     const RayQ N = P.fq[1u - P.parity];
     const uint32_t lane = lane_id();
-    uint32_t head[PT_NQ];             // done rings consumed (this wave only)
+    uint32_t head[NQ];             // done rings consumed (this wave only)
 #pragma unroll
-    for (uint32_t w = 0; w < PT_NQ; ++w) head[w] = 0u;
+    for (uint32_t w = 0; w < NQ; ++w) head[w] = 0u;
     uint32_t tail = 0u;               // ray ring published
-    uint32_t f_tail = PT_CMAX;        // pixel-table free ring: entries returned (this wave only)
+    uint32_t f_tail = CMAX;        // pixel-table free ring: entries returned (this wave only)
     SProf pf;                         // (diagnostics builds only: PT_WPROF)
     uint32_t prog = 0u;               // finished samples not yet added to P.progress
     // ended paths waiting for their fold (this wave's own queue: {slot | miss << 31, table entry})
-    uint2* endq = P.endq + (size_t)blockIdx.x * PT_CMAX;
+    uint2* endq = P.endq + (size_t)blockIdx.x * CMAX;
     uint32_t e_head = 0u, e_tail = 0u;
     if (karg<WaveParams>().side_flags & PT_SHADE_HOLD) {
         // (test hook: the query waves of a round with a budget leave by themselves)
@@ -510,13 +527,13 @@ __device__ __forceinline__ void path_shade_wave(const WaveParams& P, PathLds& L)
         const uint32_t* in = K.ctl + PT_CTL_SET * K.parity;
         const uint32_t n_total = K.pin ? K.pin_n : in[C_FRESH] + in[C_CARRY];
         if (n_total > K.path_runend)
-            while (__builtin_amdgcn_readfirstlane(lds_read(L.qw_done)) != PT_NQ) __builtin_amdgcn_s_sleep(2);
+            while (__builtin_amdgcn_readfirstlane(lds_read(L.qw_done)) != NQ) __builtin_amdgcn_s_sleep(2);
     }
     for (;;) {
         // published entries of the done rings (ring indices are compile-time: no scratch)
-        uint32_t av[PT_NQ], total = 0u;
+        uint32_t av[NQ], total = 0u;
 #pragma unroll
-        for (uint32_t w = 0; w < PT_NQ; ++w) {
+        for (uint32_t w = 0; w < NQ; ++w) {
             av[w] = __builtin_amdgcn_readfirstlane(lds_read(L.dq_tail[w])) - head[w];
             total += av[w];
         }
@@ -530,7 +547,7 @@ __device__ __forceinline__ void path_shade_wave(const WaveParams& P, PathLds& L)
             const uint32_t n = pend < 64u ? pend : 64u;
             have = lane < n;
             uint2 v = make_uint2(0u, 0u);
-            if (have) v = endq[(e_head + lane) % PT_CMAX];
+            if (have) v = endq[(e_head + lane) % CMAX];
             pf.end_read(n, v.x);
             if (have) {
                 slot = v.x & 0x7fffffffu;
@@ -541,11 +558,11 @@ __device__ __forceinline__ void path_shade_wave(const WaveParams& P, PathLds& L)
             pf.end_done(emit ? f2u(ray.d.x) : 0u);
             e_head += n;
         } else if (total == 0u) {
-            if (lds_read(L.qw_done) == PT_NQ) {
+            if (lds_read(L.qw_done) == NQ) {
                 // every query wave has left (and published): one more look, then done
                 uint32_t left = 0u;
 #pragma unroll
-                for (uint32_t w = 0; w < PT_NQ; ++w) left += lds_read(L.dq_tail[w]) - head[w];
+                for (uint32_t w = 0; w < NQ; ++w) left += lds_read(L.dq_tail[w]) - head[w];
                 if (__builtin_amdgcn_readfirstlane(left) == 0u) break;   // (no ended path waits: see above)
                 continue;
             }
@@ -555,14 +572,14 @@ __device__ __forceinline__ void path_shade_wave(const WaveParams& P, PathLds& L)
         } else {
             // up to 64 of them: a fair share of each ring first (a full ring holds back its
             // producer's finished queries), then the rest in ring order
-            uint32_t take[PT_NQ], n = 0u;
+            uint32_t take[NQ], n = 0u;
 #pragma unroll
-            for (uint32_t w = 0; w < PT_NQ; ++w) {
-                take[w] = av[w] < 64u / PT_NQ ? av[w] : 64u / PT_NQ;
+            for (uint32_t w = 0; w < NQ; ++w) {
+                take[w] = av[w] < 64u / NQ ? av[w] : 64u / NQ;
                 n += take[w];
             }
 #pragma unroll
-            for (uint32_t w = 0; w < PT_NQ; ++w) {
+            for (uint32_t w = 0; w < NQ; ++w) {
                 const uint32_t x = av[w] - take[w] < 64u - n ? av[w] - take[w] : 64u - n;
                 take[w] += x;
                 n += x;
@@ -571,12 +588,12 @@ __device__ __forceinline__ void path_shade_wave(const WaveParams& P, PathLds& L)
             // this lane's entry: ring w, position head[w] + (lane - entries of the rings before w)
             uint32_t j = 0u, before = 0u;
 #pragma unroll
-            for (uint32_t w = 0; w < PT_NQ; ++w) {
+            for (uint32_t w = 0; w < NQ; ++w) {
                 if (lane >= before && lane < before + take[w]) j = w * PT_DQN + (head[w] + lane - before) % PT_DQN;
                 before += take[w];
             }
 #pragma unroll
-            for (uint32_t w = 0; w < PT_NQ; ++w) head[w] += take[w];
+            for (uint32_t w = 0; w < NQ; ++w) head[w] += take[w];
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             have = lane < n;
             F4 o = F4{0.f, 0.f, 0.f, 0.f}, d = o;
@@ -588,7 +605,7 @@ __device__ __forceinline__ void path_shade_wave(const WaveParams& P, PathLds& L)
             // the entries are in registers: their slots go back to the producers
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
 #pragma unroll
-            for (uint32_t w = 0; w < PT_NQ; ++w)
+            for (uint32_t w = 0; w < NQ; ++w)
                 if (lane == w) lds_write(L.dq_head[w], head[w]);
             pf.read_done();
             bool miss = false;
@@ -596,12 +613,12 @@ __device__ __forceinline__ void path_shade_wave(const WaveParams& P, PathLds& L)
                 slot = f2u(o.w);
                 ray.o = mk3(o.x, o.y, o.z);
                 ray.d = mk3(d.x, d.y, d.z);
-                emit = vertex_item(P, EmitPath{L, P.S}, L.H, cid, slot, ray, f2u(d.w), miss);
+                emit = vertex_item(P, EmitPath<PathLds<NQ>>{L, P.S}, L.H, cid, slot, ray, f2u(d.w), miss);
             }
             // ended paths wait for a fold batch of their own (appended in lane order)
             const bool ended = have && !emit;
             const unsigned long long me = __ballot(ended);
-            if (ended) endq[(e_tail + lanes_below(me)) % PT_CMAX] = make_uint2(slot | (miss ? 0x80000000u : 0u), cid);
+            if (ended) endq[(e_tail + lanes_below(me)) % CMAX] = make_uint2(slot | (miss ? 0x80000000u : 0u), cid);
             e_tail += (uint32_t)__popcll(me);
             have = have && emit;   // (an ended path is not gone: its pixel waits for the fold)
             pf.shaded();
@@ -613,13 +630,13 @@ __device__ __forceinline__ void path_shade_wave(const WaveParams& P, PathLds& L)
             if (pg && lane == 0u) __hip_atomic_fetch_add(pg, (unsigned long long)prog, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             if (pg) prog = 0u;
         }
-        const bool flush = __builtin_amdgcn_readfirstlane(lds_read(L.qw_done)) == PT_NQ;
+        const bool flush = __builtin_amdgcn_readfirstlane(lds_read(L.qw_done)) == NQ;
         const unsigned long long me = __ballot(emit);
         // pixels done with this pass (end_item wrote their records back): their table entries are free
         const bool fin = have && !emit;
         const unsigned long long mf = __ballot(fin);
         uint32_t gone = (uint32_t)__popcll(mf);
-        if (fin) lds_put(L.F, (f_tail + lanes_below(mf)) % PT_CMAX, (uint16_t)cid);
+        if (fin) lds_put(L.F, (f_tail + lanes_below(mf)) % CMAX, (uint16_t)cid);
         f_tail += gone;
         if (flush) {
             // no query wave left to take it: the next round's fresh queue (the chain leaves
@@ -637,10 +654,10 @@ __device__ __forceinline__ void path_shade_wave(const WaveParams& P, PathLds& L)
         } else {
             if (emit) {
                 // the next ray into the LDS ray ring (RayQ form: push_ray's plane test and set-up)
-                const uint32_t e = (tail + lanes_below(me)) % PT_CMAX;
+                const uint32_t e = (tail + lanes_below(me)) % CMAX;
                 float pt;
                 int pid;
-                q_planes_e(P.S, PlanesPath{L, P.S}, ray, pt, pid);
+                q_planes_e(P.S, PlanesPath<PathLds<NQ>>{L, P.S}, ray, pt, pid);
                 lds_put(L.rq_ro, e, F4{ray.o.x, ray.o.y, ray.o.z, u2f(slot)});
                 lds_put(L.rq_rd, e, F4{ray.d.x, ray.d.y, ray.d.z, pt});
                 lds_put(L.rq_pid, e, pid);
@@ -670,7 +687,7 @@ __device__ __forceinline__ void path_shade_wave(const WaveParams& P, PathLds& L)
         // (the append first: ring values held across its atomic would live in scratch)
         const uint32_t k = wave_append(out + C_FRESH, has);
         if (has) {
-            const uint32_t e = i % PT_CMAX;
+            const uint32_t e = i % CMAX;
             const F4 ro = lds_get(L.rq_ro, e);
             N.ro[k] = ro;
             N.rd[k] = lds_get(L.rq_rd, e);
@@ -684,11 +701,11 @@ __device__ __forceinline__ void path_shade_wave(const WaveParams& P, PathLds& L)
 // The end-of-pass (sparse) kernel runs few chains, bound by their latency, not by
 // occupancy: it is held to 2 waves per SIMD (256 VGPRs, no spills; 2 workgroups per CU
 // run at a time, the grid's others start as those finish and find the round's work taken)
-template <bool SPARSE>
-__global__ void __launch_bounds__(PT_PATH_WG)
+template <uint32_t NQ, bool SPARSE>
+__global__ void __launch_bounds__(64u * (NQ + 1u))
 __attribute__((amdgpu_waves_per_eu(SPARSE ? 2u : PT_PATH_WAVES_PER_EU, SPARSE ? 2u : PT_PATH_WAVES_PER_EU)))
 k_wpath(WaveParams P) {
-    __shared__ PathLds L;
+    __shared__ PathLds<NQ> L;
     {
         // the first planes and emitters (the shade wave's plane tests and light sampling)
         const uint32_t npl = (P.S.n_planes < QC_NPL ? P.S.n_planes : QC_NPL) * 5u;
@@ -705,14 +722,14 @@ k_wpath(WaveParams P) {
     if (threadIdx.x == 0u) {
         L.rq_head = L.rq_tail = L.resident = L.qw_done = L.leaked = L.f_head = 0u;
     }
-    if (threadIdx.x < PT_NQ) L.dq_tail[threadIdx.x] = L.dq_head[threadIdx.x] = 0u;
-    for (uint32_t i = threadIdx.x; i < PT_CMAX; i += blockDim.x) lds_put(L.F, i, (uint16_t)i);   // every entry free
+    if (threadIdx.x < NQ) L.dq_tail[threadIdx.x] = L.dq_head[threadIdx.x] = 0u;
+    for (uint32_t i = threadIdx.x; i < PathLds<NQ>::CMAX; i += blockDim.x) lds_put(L.F, i, (uint16_t)i);   // every entry free
     wprof_start(P.wg_prof);
     __syncthreads();
-    // waves 0 .. PT_NQ-1 query, wave PT_NQ shades
+    // waves 0 .. NQ-1 query, wave NQ shades
     const uint32_t wave = threadIdx.x >> 6;
-    if (wave == PT_NQ) path_shade_wave(P, L);
-    else path_query_wave<SPARSE>(P, L, wave);
+    if (wave == NQ) path_shade_wave<NQ>(P, L);
+    else path_query_wave<NQ, SPARSE>(P, L, wave);
     // the round's finished workgroups (an early cooperative launch beside this round stops
     // once all are done: WaveParams::side_stop)
     __syncthreads();
@@ -726,18 +743,24 @@ k_wpath(WaveParams P) {
 extern "C++" {
 hipError_t pt_preload_kernels_path() {
     hipFuncAttributes a;
-    return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(pt::k_wpath<false>));
+    hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(pt::k_wpath<2u, false>));
+    if (e == hipSuccess) e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(pt::k_wpath<3u, false>));
+    return e;
 }
 
-hipError_t pt_launch_path_round(pt::WaveParams p, uint32_t path_grid, uint32_t shade_grid, hipStream_t s, bool sparse,
-                                hipEvent_t e0, hipEvent_t e1) {
+hipError_t pt_launch_path_round(pt::WaveParams p, uint32_t nq, uint32_t path_grid, uint32_t shade_grid, hipStream_t s,
+                                bool sparse, hipEvent_t e0, hipEvent_t e1) {
     hipError_t e;
+    // (the end-of-pass kernel has the one shape)
+    if ((nq != 2u && nq != 3u) || (sparse && nq != 2u)) return hipErrorInvalidValue;
     p.path = 1u;
     if (e0 && (e = hipEventRecord(e0, s)) != hipSuccess) return e;
     if (sparse)
-        hipLaunchKernelGGL(pt::k_wpath<true>, dim3(path_grid), dim3(PT_PATH_WG), 0, s, p);
+        hipLaunchKernelGGL((pt::k_wpath<2u, true>), dim3(path_grid), dim3(192), 0, s, p);
+    else if (nq == 3u)
+        hipLaunchKernelGGL((pt::k_wpath<3u, false>), dim3(path_grid), dim3(256), 0, s, p);
     else
-        hipLaunchKernelGGL(pt::k_wpath<false>, dim3(path_grid), dim3(PT_PATH_WG), 0, s, p);
+        hipLaunchKernelGGL((pt::k_wpath<2u, false>), dim3(path_grid), dim3(192), 0, s, p);
     if (e1 && (e = hipEventRecord(e1, s)) != hipSuccess) return e;
     if ((e = hipGetLastError()) != hipSuccess) return e;
     return pt_launch_exact_shade(p, shade_grid, s);

@@ -10,6 +10,14 @@
 namespace pt {
 
 #ifdef PT_WPROF
+// -DPT_WPROF_LIGHT besides: the query waves only count their trips and sample the rings (no clock
+// reads, no per-kind ballots), the shade wave's profile is whole.  The full profile slows a query
+// trip, and so the demand on the shade wave: its load at the product's rate shows only in this form.
+#ifdef PT_WPROF_LIGHT
+constexpr bool kWprofLight = true;
+#else
+constexpr bool kWprofLight = false;
+#endif
 struct QProf {
     uint64_t trips = 0, act = 0, sleep_ = 0, ring_ = 0, pulled_ = 0, exit_budget_ = 0, res = 0, dq = 0, rq = 0;
     uint64_t tripcyc = 0, refillcyc = 0, stepcyc = 0, auxtrips = 0, picktrips = 0, stepped = 0, donecyc = 0;
@@ -24,7 +32,7 @@ struct QProf {
     template <class LL>
     __device__ void trip(uint32_t nidle, const LL& L, uint32_t wq) {
         auto rd = [](const uint32_t& v) { return *(const volatile uint32_t*)&v; };
-        const uint64_t t = __builtin_amdgcn_s_memtime();
+        const uint64_t t = kWprofLight ? t0 : __builtin_amdgcn_s_memtime();
         tripcyc += t - t0;
         t0 = t;
         trips++;
@@ -36,20 +44,23 @@ struct QProf {
     __device__ void exit_budget() { exit_budget_ = 1; }
     __device__ void ring(uint32_t n) { ring_ += n; }
     __device__ void pulled(uint32_t n) { pulled_ += n; }
-    __device__ void query_start() { qstart = __builtin_amdgcn_s_memtime(); qs = 0; }
+    __device__ void query_start() { if (kWprofLight) return; qstart = __builtin_amdgcn_s_memtime(); qs = 0; }
     __device__ void sleep() { sleep_++; }
     __device__ void refill_end(bool active) {
+        if (kWprofLight) return;
         refillcyc += __builtin_amdgcn_s_memtime() - t0;
         if (active) qs++;
         s0 = __builtin_amdgcn_s_memtime();
     }
     __device__ void kinds(bool aux_lane, bool pick, bool stepped_lane) {
+        if (kWprofLight) return;
         if (__ballot(aux_lane) != 0ull) auxtrips++;
         if (pick) picktrips++;
         stepped += (uint64_t)__popcll(__ballot(stepped_lane));
     }
     // cat: this lane's step kind in the trip's step (> 4: none)
     __device__ void kind_mix(uint32_t cat) {
+        if (kWprofLight) return;
         for (uint32_t k = 0; k < 5u; ++k) {
             const unsigned long long m = __ballot(cat == k);
             if (m) {
@@ -60,21 +71,23 @@ struct QProf {
     }
     // an extra aux-node step of the same trip, for n lanes
     __device__ void extra_aux(uint32_t n) {
+        if (kWprofLight) return;
         kiss[0]++;
         klanes[0] += n;
     }
     __device__ void step_end() {
+        if (kWprofLight) return;
         s1 = __builtin_amdgcn_s_memtime();
         stepcyc += s1 - s0;
     }
     __device__ void query_done() {
-        if (qstart) {
+        if (!kWprofLight && qstart) {
             qlat += __builtin_amdgcn_s_memtime() - qstart;
             qn++;
             qsteps += qs;
         }
     }
-    __device__ void done_end() { donecyc += __builtin_amdgcn_s_memtime() - s1; }
+    __device__ void done_end() { if (kWprofLight) return; donecyc += __builtin_amdgcn_s_memtime() - s1; }
     __device__ void store(unsigned long long* prof, uint64_t rays) const {
         if (!prof) return;
         unsigned long long* w = prof + 64ull * blockIdx.x;

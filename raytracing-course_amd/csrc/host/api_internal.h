@@ -143,6 +143,12 @@ int handoff_site(const char* name);
 // a scene beyond the cooperative engine's LDS tables (RAY_DEPTH > QC_FOLD, more than
 // QC_NPL planes or QC_NEM emitters) runs its BIG instantiation
 bool coop_big(const pt_session* ss);
+// a path round's launch shape: query waves per workgroup, workgroups, and the chains a
+// workgroup holds at most.  Full rounds (at least lowq chains, not the sparse kernel) run the
+// session's full shape; low-chain rounds, the sparse kernel and a round beside the early
+// cooperative launch (`side`: its workgroup's LDS must fit beside the round's) NQ = 2.
+struct PathShape { uint32_t nq, grid, cmax; };
+PathShape path_shape(const pt_session* ss, uint32_t chains, bool sparse, bool side);
 
 static_assert(pt::HO_SUSPEND == PT_HO_SUSPEND && pt::HO_FLUSH == PT_HO_FLUSH && pt::HO_RINGOUT == PT_HO_RINGOUT &&
                   pt::HO_EXACT == PT_HO_EXACT && pt::HO_SIDE_TAKE == PT_HO_SIDE_TAKE &&
@@ -204,6 +210,10 @@ struct pt_session {
     // wavefront engine buffers (replay traversal)
     bool wave = false;
     uint32_t path_grid = 0, path_budget = 1024, path_ticks = 0, low_ticks = 0, path_runend = 0, path_sparse = 0, sparse_steps = 8;
+    // the full rounds' shape: query waves per workgroup (PT_TUNE nq: 2 or 3) and its grid; path_grid is
+    // the grid of the NQ = 2 launches (low-chain rounds at most low_grid of it, the sparse kernel)
+    uint32_t full_nq = PT_NQ_FULL, full_grid = 0;
+    bool runend_auto = false;     // path_runend follows the launch's shape (a few chains per query wave)
     uint32_t coop_max = 0, coop_grid = 0, coop_reserve = 0;   // cooperative engine (k_wcoop) at the end of a pass
     uint32_t round_batch = 1;     // rounds launched per count while the chains are far above the hand-over
     // k_wpath's per-trip step mix: {probe_every, probe_min, aux_extra, end_min}, and the one of
@@ -238,7 +248,7 @@ struct pt_session {
     pt::DoneQ done = {};          // exact-DFS results (n_slots)
     pt::RayQ ex = {};             // rays handed to the exact DFS (n_slots)
     uint32_t* carry = nullptr;    // 2 * carry_cap * carry_words
-    uint2* endq = nullptr;        // path_grid * PT_CMAX: the shade waves' ended paths
+    uint2* endq = nullptr;        // grid * path_cmax(nq) of the larger shape: the shade waves' ended paths
     unsigned long long short_seen = 0;   // CTR_SHORT at the last resolve
     uint32_t lane_cap = 0;        // min(pixels, query lanes): what one round can suspend
     uint32_t carry_cap = 0, carry_words = 0;

@@ -51,6 +51,9 @@ const Rccl& rccl() {
 //   budget=N          ... trips a query wave keeps its chains after the round's work ran out, when
 //                     budget_us is 0 or budget alone is given (default 1024)
 //   wg_per_cu=N       path engine: workgroups per CU (grid)
+//   nq=2|3            path engine, full rounds: query waves per shade wave -- 2 at 4 workgroups per
+//                     CU, or 3 at 3 (low-chain rounds, the end-of-pass kernel and rounds beside the
+//                     early cooperative launch always run 2); any other value is refused
 //   runend=N          a round with at most N chains runs them to the end of the pass
 //   sparse=N          rounds with fewer than N chains run the end-of-pass kernel
 //   sparse_steps=N    steps per loop trip of the end-of-pass kernel

@@ -59,18 +59,7 @@ int fill_params(pt_session* ss, uint32_t spp, const PassTune& t, pt::WaveParams&
     wp.path = 1u;
     wp.path_budget = ss->path_budget;
     wp.path_ticks = ss->path_ticks;
-    wp.path_runend = ss->path_runend;
-    // Chains a workgroup may hold: 5/8 of the pixels' fair share, within
-    // [256, PT_CMAX].  Below the share, about a third of the chains wait in the
-    // queue and go to whichever workgroup drains first, instead of every
-    // workgroup filling to its share and the costly ones finishing last
-    // (1920x1080 on 1,024 workgroups: rank of 4 -> 319 instead of 478, +1 % over
-    // three alternating pairs; ranks of 1 and 2 stay at 512, a rank of 8 at 256).
-    {
-        const uint64_t share = ((uint64_t)ss->n_slots + ss->path_grid - 1) / std::max(1u, ss->path_grid);
-        wp.path_cap = (uint32_t)std::min<uint64_t>(PT_CMAX, std::max<uint64_t>(256u, share * 5u / 8u));
-    }
-    if (t.has_cap) wp.path_cap = std::min<uint32_t>(PT_CMAX, (uint32_t)std::max(64, t.cap));
+    // (path_runend and path_cap: per round, from its launch's shape -- path_round)
     wp.tile_order = ss->tile_order;
     wp.sparse_steps = ss->sparse_steps;
     wp.coop_reserve = ss->coop_reserve;
@@ -191,7 +180,7 @@ int report_wgprof(pt_session* ss, const pt::WaveParams& wp, uint32_t p, const ch
 }
 // roundlog >= 2: each round's chains, kind, wall time and rays (roundlog=3: also how
 // far behind the pass target the unfinished pixels are); `chains` 0 = the pass's start
-int report_round(pt_session* ss, int level, uint32_t target, uint32_t chains, bool side) {
+int report_round(pt_session* ss, int level, uint32_t target, uint32_t chains, bool side, bool sparse = false) {
     if (!chains) HIP_TRY(hipStreamSynchronize(ss->stream));
     const double now = wall_ms();
     unsigned long long c[PT_CTR_STRIDE];
@@ -199,9 +188,10 @@ int report_round(pt_session* ss, int level, uint32_t target, uint32_t chains, bo
     const unsigned long long rays = c[0];
     if (chains) {
         const double ms = now - ss->roundlog_t;
-        fprintf(stderr, "round %u chains %u -> %u+%u (%s%s) %.2f ms rays %llu %.0f Mray/s", ss->rounds, chains,
+        const PathShape sh = path_shape(ss, chains, sparse, side);
+        fprintf(stderr, "round %u chains %u -> %u+%u (%s%s, nq %u x %u) %.2f ms rays %llu %.0f Mray/s", ss->rounds, chains,
                 ss->ctl_host[pt::C_FRESH], ss->ctl_host[pt::C_CARRY], chains < ss->lowq ? "low" : "full",
-                side ? "+side" : "", ms, rays - ss->roundlog_rays, (rays - ss->roundlog_rays) / ms / 1e3);
+                side ? "+side" : "", sh.nq, sh.grid, ms, rays - ss->roundlog_rays, (rays - ss->roundlog_rays) / ms / 1e3);
         if (level == 3) {
             std::vector<uint4> rec(2ull * ss->n_slots);
             HIP_TRY(hipMemcpy(rec.data(), ss->st.rec, rec.size() * sizeof(uint4), hipMemcpyDeviceToHost));
@@ -324,8 +314,8 @@ struct SideLate {
 };
 // k = the chains it takes (> 0); the round's output set is zero already (zero_round_out)
 int side_launch(pt_session* ss, const PassTune& t, pt::WaveParams& wp, uint32_t p, uint32_t chains, uint32_t k,
-                SideLate& late) {
-    const uint32_t path_grid = chains < ss->lowq && ss->low_grid ? ss->low_grid : ss->path_grid;
+                bool sparse, SideLate& late) {
+    const uint32_t path_grid = path_shape(ss, chains, sparse, true).grid;   // (the round's workgroups: path_round)
     if (ss->side_th.joinable()) {
         ss->side_th.join();
         if (ss->side_rc != hipSuccess) return fail(PT_E_HIP, "side stream creation failed");
@@ -390,7 +380,7 @@ int path_round(pt_session* ss, const PassTune& t, pt::WaveParams& wp, uint32_t p
     if (!t.wgprof.empty()) TRY(arm_wg_prof(ss, wp, 512ull * ss->path_grid));
     hipEvent_t i0, i1;
     TRY(launch_events(ss, false, i0, i1));
-    uint32_t grid = ss->path_grid;
+    const PathShape sh = path_shape(ss, chains, sparse, wp.pin != nullptr);   // (pin: beside the early launch)
     const bool low = chains < ss->lowq;
     wp.path_ticks = low ? ss->low_ticks : ss->path_ticks;
     const uint32_t* m = low ? ss->mix_low : ss->mix;
@@ -398,11 +388,23 @@ int path_round(pt_session* ss, const PassTune& t, pt::WaveParams& wp, uint32_t p
     wp.probe_min = m[1];
     wp.aux_extra = m[2];
     wp.end_min = m[3];
-    if (low && ss->low_grid) {
-        grid = ss->low_grid;
-        if (!t.has_cap) wp.path_cap = PT_CMAX;   // (an explicit cap=N stays)
+    // the session's grid of this shape (a low-chain round runs fewer workgroups of it)
+    const uint32_t shape_grid = sh.nq == PT_NQ_BASE ? ss->path_grid : ss->full_grid;
+    wp.path_runend = ss->runend_auto ? shape_grid * sh.nq * 4u : ss->path_runend;
+    // Chains a workgroup may hold: 5/8 of the pixels' fair share, within
+    // [256, the shape's capacity].  Below the share, about a third of the chains wait in
+    // the queue and go to whichever workgroup drains first, instead of every
+    // workgroup filling to its share and the costly ones finishing last
+    // (1920x1080 on 1,024 workgroups: rank of 4 -> 319 instead of 478, +1 % over
+    // three alternating pairs; ranks of 1 and 2 stay at 512, a rank of 8 at 256).
+    // A low-chain round's workgroups take the whole capacity.
+    {
+        const uint64_t share = ((uint64_t)ss->n_slots + shape_grid - 1) / std::max(1u, shape_grid);
+        wp.path_cap = (uint32_t)std::min<uint64_t>(sh.cmax, std::max<uint64_t>(256u, share * 5u / 8u));
     }
-    HIP_TRY(pt_launch_path_round(wp, grid, 64u, ss->stream, sparse, i0, i1));
+    if (low && ss->low_grid) wp.path_cap = sh.cmax;
+    if (t.has_cap) wp.path_cap = std::min<uint32_t>(sh.cmax, (uint32_t)std::max(64, t.cap));   // (an explicit cap=N stays)
+    HIP_TRY(pt_launch_path_round(wp, sh.nq, sh.grid, 64u, ss->stream, sparse, i0, i1));
     wp.pin = nullptr;   // (only the round beside the early launch skips its chains)
     return PT_OK;
 }
@@ -445,7 +447,7 @@ int trace_wave(pt_session* ss, uint32_t spp) {
         SideLate late;
         for (uint32_t r = 0; r < batch; ++r) {
             HIP_TRY(zero_round_out(ss, p));
-            if (k) TRY(side_launch(ss, t, wp, p, chains, k, late));
+            if (k) TRY(side_launch(ss, t, wp, p, chains, k, sparse, late));
             TRY(path_round(ss, t, wp, p, chains, sparse));
             if (late.on) TRY(side_launch_late(ss, late));
             if (!t.wgprof.empty()) TRY(report_wgprof(ss, wp, p, t.wgprof.c_str()));
@@ -455,7 +457,7 @@ int trace_wave(pt_session* ss, uint32_t spp) {
         // (a side launch yields into this round's output: the count waits for it)
         if (k) HIP_TRY(hipStreamWaitEvent(ss->stream, ss->side_end, 0));
         TRY(count_round(ss, p));
-        if (t.roundlog >= 2) TRY(report_round(ss, t.roundlog, wp.target, chains, k != 0u));
+        if (t.roundlog >= 2) TRY(report_round(ss, t.roundlog, wp.target, chains, k != 0u, sparse));
         if (t.dupcheck) TRY(check_dups(ss, wp, p, chains, k != 0u));
         if (ss->ctl_host[pt::C_FRESH] == 0u && ss->ctl_host[pt::C_CARRY] == 0u) break;
         if (guard > 100000u) return fail(PT_E_HIP, "wavefront rounds did not drain");

@@ -106,6 +106,12 @@ pt::SceneView device_view(const pt_session* ss) {
     return v;
 }
 
+PathShape path_shape(const pt_session* ss, uint32_t chains, bool sparse, bool side) {
+    if (chains < ss->lowq && ss->low_grid) return {PT_NQ_BASE, ss->low_grid, pt::path_cmax(PT_NQ_BASE)};
+    if (sparse || side || ss->full_nq == PT_NQ_BASE) return {PT_NQ_BASE, ss->path_grid, pt::path_cmax(PT_NQ_BASE)};
+    return {ss->full_nq, ss->full_grid, pt::path_cmax(ss->full_nq)};
+}
+
 bool coop_big(const pt_session* ss) {
     const pt_scene* s = ss->sc;
     return ss->depth > QC_FOLD || s->planes.size() > QC_NPL || s->emitters.size() > QC_NEM;
@@ -177,7 +183,7 @@ int pt_session_create(pt_scene* s, const pt_session_opts* o, pt_session** out) {
     std::vector<uint32_t> ord;   // wavefront: the local tiles' seeding order
     if (ss->wave) {
         ss->shade_grid = std::min<uint32_t>(cus * 8u, std::max(1u, ss->n_tiles_local));
-        // path engine: PT_NQ query waves + 1 shade wave per workgroup, as many workgroups
+        // path engine: NQ query waves + 1 shade wave per workgroup, as many workgroups
         // per CU as its waves-per-SIMD occupancy holds (4 SIMDs per CU)
         ss->path_budget = (uint32_t)std::max(1, tune_int("budget", (int)ss->path_budget));
         // rounds end at one time for every wave (budget_us after the work ran out; 0: each
@@ -193,8 +199,17 @@ int pt_session_create(pt_scene* s, const pt_session_opts* o, pt_session** out) {
         ss->low_ticks = tune_has("lowq_budget_us")
                             ? (uint32_t)std::min(10000000, std::max(0, tune_int("lowq_budget_us", 5000))) * 100u
                             : ss->path_ticks == 0 ? 0u : 500000u;
-        const int wg_cu = std::max(1, (int)(PT_PATH_WAVES_PER_EU * 4u / (PT_NQ + 1u)));
-        ss->path_grid = cus * (uint32_t)std::max(1, tune_int("wg_per_cu", wg_cu));
+        // (the full rounds' shape, PT_TUNE nq: 2, or 3 query waves per shade wave at 3 workgroups per CU)
+        if (tune_has("nq")) {
+            const std::string v = tune_str("nq");
+            if (v != "2" && v != "3")
+                return cleanup(fail(PT_E_INVALID, "PT_TUNE nq=" + v + ": no such shape (2 or 3 query waves per workgroup)"));
+            ss->full_nq = v == "3" ? 3u : 2u;
+        }
+        ss->path_grid = cus * (uint32_t)std::max(1, tune_int("wg_per_cu", (int)pt::path_wg_per_cu(PT_NQ_BASE)));
+        ss->full_grid = cus * (uint32_t)std::max(1, tune_int("wg_per_cu", (int)pt::path_wg_per_cu(ss->full_nq)));
+        // the query lanes of the larger launch
+        const uint64_t lanes = std::max<uint64_t>((uint64_t)ss->path_grid * PT_NQ_BASE, (uint64_t)ss->full_grid * ss->full_nq) * 64u;
         // suspended-query records: Query | slot | aux stack, rounded to 16 B.  Only a
         // query lane suspends (one query at round end), and a pixel has at most one ray
         // in flight, so a round appends at most min(pixels, query lanes) of them: the
@@ -204,14 +219,14 @@ int pt_session_create(pt_scene* s, const pt_session_opts* o, pt_session** out) {
         // at most one per pixel (a chain that leaves for k_wexact leaves the round).
         // They hold n entries.
         ss->carry_words = ((uint32_t)(sizeof(pt::Query) / 4) + 1u + std::max<uint32_t>(s->auxw_stack, 1u) + 3u) & ~3u;
-        ss->lane_cap = (uint32_t)std::min<uint64_t>(n, (uint64_t)ss->path_grid * PT_NQ * 64u);
+        ss->lane_cap = (uint32_t)std::min<uint64_t>(n, lanes);
         ss->carry_cap = ss->lane_cap;
         // a round whose chains are this few runs them to the end of the pass (a few
-        // per query wave: rebalancing them costs more rounds than it saves)
-        ss->path_runend = ss->path_grid * PT_NQ * 4u;
-        ss->path_runend = (uint32_t)std::max(0, tune_int("runend", (int)ss->path_runend));
-        // rounds with fewer chains than this run the end-of-pass (sparse) kernel
-        ss->path_sparse = ss->path_grid * PT_NQ * 32u;
+        // per query wave of its launch, 4: rebalancing them costs more rounds than it saves)
+        ss->runend_auto = !tune_has("runend");
+        ss->path_runend = (uint32_t)std::max(0, tune_int("runend", 0));
+        // rounds with fewer chains than this run the end-of-pass (sparse) kernel (its own shape's lanes)
+        ss->path_sparse = ss->path_grid * PT_NQ_BASE * 32u;
         ss->path_sparse = (uint32_t)std::max(0, tune_int("sparse", (int)ss->path_sparse));
         ss->sparse_steps = (uint32_t)std::max(1, tune_int("sparse_steps", (int)ss->sparse_steps));
         // a round whose chains are at most this many runs the cooperative engine (one
@@ -248,7 +263,10 @@ int pt_session_create(pt_scene* s, const pt_session_opts* o, pt_session** out) {
         else ss->coop_reserve = reserve;
         // with the cooperative engine the path engine never runs a round to the end:
         // its rounds stay budget-limited, so the host sees the chains fall below coop_max
-        if (ss->coop_max && !tune_has("runend")) ss->path_runend = 0;
+        if (ss->coop_max && ss->runend_auto) {
+            ss->path_runend = 0;
+            ss->runend_auto = false;
+        }
         // ... and the end-of-pass (sparse) path kernel, whose rounds are long, never runs
         // above the hand-over
         if (ss->coop_max && !tune_has("sparse")) ss->path_sparse = std::min(ss->path_sparse, ss->coop_max);
@@ -345,7 +363,8 @@ int pt_session_create(pt_scene* s, const pt_session_opts* o, pt_session** out) {
             a_hid = sec(n * 4);
             a_carry = sec(2ull * ss->carry_cap * ss->carry_words * 4);
             a_ctl = sec(8 * PT_CTL_SET);
-            a_endq = sec((size_t)ss->path_grid * PT_CMAX * sizeof(uint2));
+            a_endq = sec(std::max((size_t)ss->path_grid * pt::path_cmax(PT_NQ_BASE),
+                                  (size_t)ss->full_grid * pt::path_cmax(ss->full_nq)) * sizeof(uint2));
             a_order = sec((n + 2 * PT_ORDER_BUCKETS) * 4);
             if (ss->early_k) {
                 for (int k = 0; k < 3; ++k) a_side[k] = sec((size_t)ss->early_k * 16);

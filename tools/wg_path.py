@@ -7,7 +7,7 @@ import sys
 import numpy as np
 
 G = int(sys.argv[2])
-NQ = int(sys.argv[3]) if len(sys.argv) > 3 else 2   # query waves per workgroup (PT_NQ)
+NQ = int(sys.argv[3]) if len(sys.argv) > 3 else 2   # query waves per workgroup of the full rounds (PT_TUNE nq)
 a = np.fromfile(sys.argv[1], np.uint64).reshape(-1, G, 64).astype(np.int64)
 tot = a.sum(axis=(0, 1))
 span = []
