@@ -5,6 +5,9 @@
 #else
 #include <hip/hip_runtime_api.h>
 #endif
+#include <stddef.h>
+
+#include <type_traits>
 
 #include "pt_query.h"
 
@@ -77,7 +80,7 @@ struct DoneQ {                    // finished queries, input of the shade kernel
     F4* rd;                       // {d.xyz, -}
     uint32_t* id;                 // closest prim (the shade kernel recomputes t, n, side from it), 0xffffffff = miss
 };
-// how a path ended (shade_item)
+// how a path ended (coop_shade)
 enum : uint32_t { PE_LIVE = 0u, PE_MISS = 1u, PE_CUT = 2u, PE_TERM = 3u };
 
 // round counters: set p = ctl + PT_CTL_SET * p; the work-batch heads are one per
@@ -162,6 +165,61 @@ struct WaveParams {
     // must report (0 in every render)
     uint32_t drop;
 };
+// A suspended query's record in a carry queue (WaveParams::cq, carry_words words each):
+//   Query | pixel slot | the query lane's aux stack words (Query::sp of them)
+// The path engine resumes a query from the whole record; the cooperative engine restarts
+// it from its ray and slot alone (a query is a function of its ray), so a restart record
+// -- a query at its start -- needs only those two: the ray is the Query's first member.
+static_assert(offsetof(Query, ray) == 0, "a carry record starts with its query's ray");
+static_assert(sizeof(Query) % 4u == 0, "a carry record is addressed in words");
+constexpr uint32_t CARRY_QUERY_WORDS = (uint32_t)(sizeof(Query) / 4u);
+// a record's words for an aux stack of `stack_words`, rounded to 16 B
+constexpr uint32_t carry_record_words(uint32_t stack_words) {
+    return (CARRY_QUERY_WORDS + 1u + stack_words + 3u) & ~3u;
+}
+template <class W>   // uint32_t, or const uint32_t for a record that is only read
+struct CarryRec {
+    template <class T>
+    using As = typename std::conditional<std::is_const<W>::value, const T, T>::type;
+    W* w;
+    PT_HD As<Query>& query() const { return *reinterpret_cast<As<Query>*>(w); }
+    PT_HD As<Ray>& ray() const { return *reinterpret_cast<As<Ray>*>(w); }
+    PT_HD W& slot() const { return w[CARRY_QUERY_WORDS]; }
+    PT_HD W& stack(uint32_t j) const { return w[CARRY_QUERY_WORDS + 1u + j]; }
+    // The whole record of a query lane: its state, slot and the q.sp words of its aux stack
+    // `stk`.  (One pointer past the Query indexed by the loops, not stack(j) per word: the
+    // path engine's suspend and resume then compile to the stores and loads they always were.)
+    template <class STK>
+    PT_HD void suspend(const Query& q, uint32_t slot_, const STK& stk) const {
+        query() = q;
+        W* tail = w + CARRY_QUERY_WORDS;
+        tail[0] = slot_;
+        for (uint32_t j = 0; j < q.sp; ++j) tail[1u + j] = stk.get(j);
+    }
+    template <class STK>
+    PT_HD void resume(Query& q, uint32_t& slot_, STK& stk) const {
+        q = query();
+        W* tail = w + CARRY_QUERY_WORDS;
+        slot_ = tail[0];
+        for (uint32_t k = 0; k < q.sp; ++k) stk.set(k, tail[1u + k]);
+    }
+};
+// record k of a queue of `words`-word records
+template <class W>
+PT_HD CarryRec<W> carry_rec(W* queue, uint32_t k, uint32_t words) { return CarryRec<W>{queue + (size_t)k * words}; }
+// A restart record, a query at its start: the whole Query (a record the path engine may
+// resume: coop_restart) ...
+PT_HD void carry_put_restart(CarryRec<uint32_t> r, const Query& q, uint32_t slot) {
+    r.query() = q;
+    r.slot() = slot;
+}
+// ... or its ray alone (k_side_take: only the cooperative engine reads these records, and
+// it reads ray() and slot(), never query())
+PT_HD void carry_put_restart(CarryRec<uint32_t> r, const Ray& ray, uint32_t slot) {
+    r.ray() = ray;
+    r.slot() = slot;
+}
+
 // k_wcoop beside a path round, test hooks (PT_TUNE side_late / handon): every workgroup
 // behaves as one that started after the round's end (takes nothing, hands every item on);
 // the untaken items are dropped instead of handed on (a lost chain: the resolve's check)
@@ -245,6 +303,15 @@ constexpr uint32_t path_wg_per_cu(uint32_t nq) { return PT_PATH_WAVES_PER_EU * 4
 #define QC_WAVES 4u
 #endif
 #define QC_SCAP_MIN 128u           // aux stack words per team (the smallest; also the exact DFS stack)
+// The engine's LDS capacities for teams of t lanes (QcTeamLds / QcPoolLds, and the host's
+// admission of a scene to a team size).  Aux stack words per chain (also its leader's exact
+// DFS stack): a whole-wave team's own; smaller teams share their wave's pool, this many words
+// per chain (teams of 4: 64, so that their wave's pool -- 16 chains -- stays at 1,024 words)
+constexpr uint32_t qc_stack_words(uint32_t t) { return t == 64u ? 448u : t == 32u ? 192u : t == 4u ? 64u : QC_SCAP_MIN; }
+// ... the pool's words per wave (teams below 64)
+constexpr uint32_t qc_pool_words(uint32_t t) { return qc_stack_words(t) * (64u / t); }
+// ... and its items, chain << shift | node: an aux entry index must stay below 2^shift
+constexpr uint32_t qc_item_shift(uint32_t t) { return 64u / t > 8u ? 28u : 29u; }
 #ifndef QC_EPL
 #define QC_EPL 1u                  // aux entries a team lane tests per expansion round (nodes per round:
                                    // QC_EPL x team / 4)

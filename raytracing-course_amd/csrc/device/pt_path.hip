@@ -1,77 +1,38 @@
-// pt_path.hip -- the path engine k_wpath: persistent, warp-specialised
-// workgroups of NQ query waves and one shade wave; a pixel's chain keeps going
-// inside the kernel through LDS rings.  pt_wave.h has the pass's outline.
-#include "pt_wave.h"
-
-namespace pt {
-
-// ---- path engine -------------------------------------------------------------
-// k_wpath: persistent and warp-specialised.  A workgroup is NQ query waves
-// plus one shade wave (NQ = 2, or 3 in the full rounds: pt_kernels.h path_cmax).  A pixel's chain (its one ray in flight) is always in
-// exactly one place: a query lane, the done ring (query finished, waiting to be
-// shaded), a shade lane, or the ray ring (its next ray, waiting for a query
-// lane).  Query lanes refill from the ray ring first and from the round's work
+// pt_path.hip -- the path engine k_wpath (pt_wave.h has the pass's outline):
+// persistent and warp-specialised.  A workgroup is NQ query waves plus one shade wave
+// (NQ = 2, or 3 in the full rounds: pt_kernels.h path_cmax).  A pixel's chain (its one
+// ray in flight) is always in exactly one place: a query lane, the done ring (query
+// finished, waiting to be shaded), a shade lane, or the ray ring (its next ray, waiting
+// for a query lane).  Query lanes refill from the ray ring first and from the round's work
 // (suspended queries, then fresh rays) second, so a chain keeps going inside the
 // kernel instead of advancing one query per round -- with fewer pixels than
 // lanes (a rank of a multi-GPU render, the end of a pass) the lanes stay busy.
 // Once the round's work is used up a query wave keeps its chains going until the
 // round's deadline (`path_ticks` after the first wave found the work used up: all
 // waves stop together; or `path_budget` more trips of its own), then suspends its
-// queries to the carry queue; the
-// shade wave, last out, hands the remaining chains' next rays to the fresh queue
-// of the next round.  Rounds then only rebalance chains between workgroups.
-//
-// LDS accessors with the address space spelled out (a reference to a __shared__ member is a
+// queries to the carry queue; the shade wave, last out, hands the remaining chains'
+// next rays to the fresh queue of the next round.  Rounds then only rebalance chains
+// between workgroups.
+#include "pt_wave.h"
 
-// The shade wave's halves of shade_item, with the pixel record in the workgroup's
-// LDS table (entry cid, PathLds::H) instead of HBM.  vertex_item: the vertex
-// (src/scene.cpp:91-177) and its fold record; true with `ray` = the child ray, or
-// false when the path ended (the miss, or the vertex ends it), `miss` telling how.
-// end_item: the backward fold into the sum (src/scene.cpp:198) and the next sample's
-// camera ray, run later in a batch of ended paths; false = the pixel reached the
-// pass target (its record is then written back to HBM).  A pixel has one chain, and
-// its next sample starts only from end_item, so its operations keep shade_item's order.
+namespace pt {
+
+// The shade wave's two steps (pt_wave.h vertex_step / end_step) with the pixel record in
+// the workgroup's LDS table (entry cid, PathLds::H) instead of HBM.  end_item runs later,
+// in a batch of ended paths; when the pixel has reached the pass target its record is
+// written back to HBM.
 template <class EM>
 __device__ __forceinline__ bool vertex_item(const WaveParams& P, const EM& em, uint4* H, uint32_t cid, uint32_t slot,
                                             Ray& ray, uint32_t hid, bool& miss) {
     PixelHot hot = hot_unpack(lds_get(H, cid));
-    uint32_t nv = hot.nv;
-    Rng R = hot.R;
-    bool live = false;
-    miss = hid == 0xffffffffu;
-    if (!miss) {
-        Hit h;
-        (void)prim_intersect(P.S.prims[hid], ray, h);
-        uint32_t idm;
-        float s1, s2;
-        const bool cont = shade_vertex_e(P.S, em, P.S.shade[hid], R, ray, h, (int)hid, idm, s1, s2);
-        HbmVStore vs = fold_store(P.st, slot);
-        vs.put(nv, idm, s1, s2);
-        ++nv;
-        live = cont && nv < P.depth;   // RayTrace(.., 0) = 0
-    }
-    hot.nv = nv;
-    hot.R = R;
+    const bool live = vertex_step(P, em, hot, slot, ray, hid, miss);
     lds_put(H, cid, hot_pack(hot));
     return live;
 }
 __device__ __forceinline__ bool end_item(const WaveParams& P, uint4* H, uint32_t cid, uint32_t slot, bool miss,
                                          Ray& ray) {
     PixelHot hot = hot_unpack(lds_get(H, cid));
-    Rng R = hot.R;
-    uint32_t pix;
-    const f3 sum = fold_path(P.st, P.S.shade, slot, hot.nv, miss ? P.S.bg : mk3(0.f, 0.f, 0.f), pix);
-    store_sum(P.st, slot, sum, pix);
-    hot.done += 1u;
-    hot.nv = 0u;
-    bool emit = false;
-    if (hot.done < P.target) {
-        // (the camera block read here, not held in SGPRs across the shade wave's loop)
-        const WaveParams& K = karg<WaveParams>();
-        ray = camera_sample(K.cam, R, pix % K.tm.W, pix / K.tm.W);
-        emit = true;
-    }
-    hot.R = R;
+    const bool emit = end_step(P, hot, slot, miss, ray);
     if (emit) lds_put(H, cid, hot_pack(hot));
     else store_hot(P.st, slot, hot);   // the pixel leaves the workgroup
     return emit;
@@ -165,8 +126,6 @@ struct EmitPath {
     }
 };
 
-
-
 #ifndef PT_PATH_REFILL_MIN
 #define PT_PATH_REFILL_MIN 8u      // idle lanes before a query wave refills (any, once the round's work is out;
                                    // 4 / 16 measured -1 % / -1.5 % in round 3)
@@ -174,106 +133,336 @@ struct EmitPath {
 #define PT_NOWORK 0xffffffffu
 #define PT_CAPPED 0xfffffffeu
 
-// SPARSE: the kernel of the rounds at the end of a pass (few chains, heavy queries:
-// bound by each chain's latency, not by issue): a trip runs every step kind and
-// up to P.sparse_steps steps.  A separate instantiation, so its registers do not
-// weigh on the main kernel.
-template <uint32_t NQ, bool SPARSE>
-__device__ __forceinline__ void path_query_wave(const WaveParams& P, PathLds<NQ>& L, uint32_t qw) {
-    constexpr uint32_t CMAX = PathLds<NQ>::CMAX;
-    LdsMemN<64u * NQ> stk{L.stk + 64u * qw + lane_id(), P.lstack, PT_LSTACK};
-    const uint32_t p = P.parity;
-    const uint32_t* in = P.ctl + PT_CTL_SET * p;
-    uint32_t* out = P.ctl + PT_CTL_SET * (1u - p);
-    const uint32_t n_carry = in[C_CARRY], n_total = P.pin ? P.pin_n : in[C_FRESH] + n_carry;
-    const uint32_t n_waves = gridDim.x * NQ;
+// ---- the query waves -----------------------------------------------------------
+// path_query_wave's loop in pieces, in the loop's order.  All are inlined into the one loop
+// and keep what its register budget rests on: a rare branch reads its parameters through
+// karg<WaveParams>() where it uses them (held in SGPRs for the loop's life they would
+// spill), and the loop has one back edge (no `continue`: a second one costs ~30 VGPRs).
+// How a piece is cut decides the registers too: a piece is simplified on its own before it
+// is inlined, so what it reaches through a reference is memory to those first passes where
+// the loop's own locals are values.  Run tools/kernel_resources.py after every change to
+// one; profiles/r09_pathsplit/README.md has what each rejected cut cost.
+
+// The round's work, as every wave of the launch reads it once
+struct PathWork {
+    uint32_t n_carry;   // suspended queries: the work items [0, n_carry), the fresh rays after them
+    uint32_t n_total;
+    uint32_t bsz;       // queue indices a wave takes per atomic
+    uint32_t budget;    // trips a query wave goes on for after the work ran out (0xffffffff: to the chains' end)
+};
+template <uint32_t NQ>
+__device__ __forceinline__ PathWork path_work(const WaveParams& P) {
+    const uint32_t* in = P.ctl + PT_CTL_SET * P.parity;
+    PathWork W;
+    W.n_carry = in[C_CARRY];
+    W.n_total = P.pin ? P.pin_n : in[C_FRESH] + W.n_carry;
     // Rounds exist to rebalance chains between workgroups.  Once the round's chains
     // fit in the query lanes (the tail of a pass: only the slowest pixels are left)
     // suspending gains nothing and costs a round: run them to the end.
-    const uint32_t budget = n_total <= P.path_runend ? 0xffffffffu : P.path_budget;
-    uint32_t bsz = n_total / n_waves;
-    bsz = bsz < 1u ? 1u : (bsz > P.batch ? P.batch : bsz);   // queue indices a wave takes per atomic
-    const RayQ FQ = P.fq[p];
+    W.budget = W.n_total <= P.path_runend ? 0xffffffffu : P.path_budget;
+    const uint32_t bsz = W.n_total / (gridDim.x * NQ);
+    W.bsz = bsz < 1u ? 1u : (bsz > P.batch ? P.batch : bsz);
+    return W;
+}
+// A query wave's counters: C per lane (the queries' steps), the others wave-level (scalar
+// registers; per-lane ones would cost VGPRs)
+// (the plane tests are rays x n_planes: every ray taken was plane-tested by its producer;
+// exact-DFS hand-offs per wave and launch stay far below 2^32)
+struct PathCounts {
+    QCounts C;
+    uint64_t rays;
+    uint32_t fallbacks, init_exact;
+};
+
+// A wave whose lanes stay busy with its workgroup's chains does not pull, so it would
+// never find the round's work used up and would run its chains to the end of the pass:
+// it looks at the 8 XCD batch counters instead (every 16th trip).
+__device__ __forceinline__ bool path_work_used(uint32_t* out, const PathWork& W) {
+    bool used = true;
+    if (lane_id() < 8u) {
+        const uint32_t h = __hip_atomic_load(out + C_HEADS + 32u * lane_id(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        used = (8ull * h + lane_id()) * W.bsz >= W.n_total;
+    }
+    return __ballot(!used) == 0ull;
+}
+// Whether the round is over for a wave that has run `wpost` trips since the work ran out:
+// never in a round that runs its chains to the end; else at the round's deadline, or
+// after the wave's trip budget.
+__device__ __forceinline__ void path_round_over(const PathWork& W, uint32_t* out, uint32_t wpost, uint32_t& deadline,
+                                                bool& over) {
+    if (W.budget == 0xffffffffu) {
+        over = false;
+    } else if (karg<WaveParams>().path_ticks) {
+        // One deadline for the whole round: the trip counts of workgroups with heavy
+        // and light chains differ, so a per-wave trip budget ends them at different
+        // times and the first ones out wait for the last (a round of a rank of 8:
+        // query waves tripping ~75 % of the round's span)
+        if (deadline == 0u) {
+            uint32_t d = 0u;
+            if (lane_id() == 0u) {
+                const uint32_t want = ((uint32_t)__builtin_amdgcn_s_memrealtime() + karg<WaveParams>().path_ticks) | 1u;
+                const uint32_t old = atomicCAS(out + C_DEADLINE, 0u, want);
+                d = old ? old : want;
+            }
+            deadline = __builtin_amdgcn_readfirstlane(d);
+        }
+        over = (int32_t)((uint32_t)__builtin_amdgcn_s_memrealtime() - deadline) >= 0;
+    } else {
+        over = wpost >= W.budget;
+    }
+}
+// The round is over for this wave: its running queries to the next carry queue (state,
+// slot, aux stack), their chains' pixel records back to HBM (hand-off site HO_SUSPEND;
+// PT_TUNE drop=suspend loses them instead)
+template <uint32_t NQ, class PF>
+__device__ __forceinline__ void path_suspend(PathLds<NQ>& L, const LdsMemN<64u * NQ>& stk, bool active, uint32_t slot,
+                                             const Query& q, PF& pf) {
+    const WaveParams& K0 = karg<WaveParams>();
+    const bool drop = K0.drop == 1u + HO_SUSPEND;
+    if (active && !drop) {
+        const WaveParams& K = karg<WaveParams>();
+        const uint32_t k = wave_append(K.ctl + PT_CTL_SET * (1u - K.parity) + C_CARRY, true);
+        carry_rec(K.cq[1u - K.parity], k, K.carry_words).suspend(q, slot, stk);
+        K.st.rec[2u * slot] = lds_get(L.H, (uint32_t)q.cid);   // the chain leaves the workgroup
+    }
+    const uint32_t ns = (uint32_t)__popcll(__ballot(active));
+    if (lane_id() == 0u && ns) {
+        atomicSub(&L.resident, ns);
+        atomicAdd(ctr_copy(K0.counters) + CTR_HO + HO_SUSPEND, (unsigned long long)ns);
+    }
+    pf.exit_budget();
+}
+
+// The refill's sources after this wave's batch leftovers (src 2 and 1 of path_start_lane).
+// The ray ring: up to `want` published entries from `h` on (the workgroup's query waves
+// compete for them: a CAS on rq_head)
+template <uint32_t NQ>
+__device__ __forceinline__ uint32_t path_ring_take(PathLds<NQ>& L, uint32_t want, uint32_t& h) {
+    uint32_t take = 0u;
+    h = 0u;
+    if (lane_id() == 0u) {
+        for (;;) {
+            h = lds_read(L.rq_head);
+            const uint32_t t = lds_read(L.rq_tail);
+            take = t - h < want ? t - h : want;
+            if (take == 0u || atomicCAS(&L.rq_head, h, h + take) == h) break;
+        }
+    }
+    h = __builtin_amdgcn_readfirstlane(h);
+    return __builtin_amdgcn_readfirstlane(take);
+}
+// A new batch of the round's work: its first item with `cnt` = its size, PT_CAPPED when
+// the workgroup is full (path_cap: its own chains first), or PT_NOWORK when the XCDs' batch
+// counters (this wave's own XCD's first; `xs` = those found empty so far) are all used up
+template <uint32_t NQ>
+__device__ __forceinline__ uint32_t path_pull_batch(const WaveParams& P, PathLds<NQ>& L, uint32_t* out, const PathWork& W,
+                                                    uint32_t xcc, uint32_t& xs, uint32_t& cnt) {
+    uint32_t v = PT_NOWORK;
+    cnt = 0u;
+    if (lane_id() == 0u) {
+        if (atomicAdd(&L.resident, W.bsz) + W.bsz + lds_read(L.leaked) > P.path_cap) {
+            atomicSub(&L.resident, W.bsz);   // workgroup full: its chains first
+            v = PT_CAPPED;
+        } else {
+            while (xs < 8u) {
+                const uint32_t y = (xcc + xs) & 7u;
+                const uint64_t b = 8ull * atomicAdd(out + C_HEADS + 32u * y, 1u) + y;
+                if (b * W.bsz < W.n_total) { v = (uint32_t)(b * W.bsz); break; }
+                ++xs;
+            }
+            if (v == PT_NOWORK) {
+                atomicSub(&L.resident, W.bsz);
+            } else {
+                cnt = W.n_total - v < W.bsz ? W.n_total - v : W.bsz;
+                if (cnt < W.bsz) atomicSub(&L.resident, W.bsz - cnt);
+            }
+        }
+    }
+    xs = __builtin_amdgcn_readfirstlane(xs);
+    cnt = __builtin_amdgcn_readfirstlane(cnt);
+    return __builtin_amdgcn_readfirstlane(v);
+}
+// A lane's refill (src, gi) started.  Chains joining the workgroup (src 1: the round's
+// work) take a pixel-table entry from the free ring (there are enough: the entries taken
+// never exceed resident + leaked <= path_cap <= CMAX); ray-ring chains bring theirs.  Then
+// the lane resumes a suspended query, or starts a fresh ray's or a ray-ring ray's.
+template <uint32_t NQ, class PF>
+__device__ __forceinline__ void path_start_lane(const WaveParams& P, PathLds<NQ>& L, const RayQ& FQ, uint32_t n_carry,
+                                                uint32_t src, uint32_t gi, LdsMemN<64u * NQ>& stk, bool& active,
+                                                uint32_t& slot, Query& q, PathCounts& N, PF& pf) {
+    constexpr uint32_t CMAX = PathLds<NQ>::CMAX;
+    const unsigned long long mjoin = __ballot(src == 1u);
+    uint32_t fh = 0u;
+    if (mjoin) {
+        if (lane_id() == 0u) fh = atomicAdd(&L.f_head, (uint32_t)__popcll(mjoin));
+        fh = __builtin_amdgcn_readfirstlane(fh);
+    }
+    if (src != 0u) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    uint32_t cid = 0u;
+    if (src == 1u) cid = lds_get(L.F, (fh + lanes_below(mjoin)) % CMAX);
+    if (src == 2u) cid = lds_get(L.rq_cid, gi);
+    if (src == 1u) {
+        const uint32_t* pin = karg<WaveParams>().pin;
+        if (pin) gi = pin[gi];   // (the early cooperative launch took the other items)
+    }
+    bool took = false;   // a fresh ray (not a resumed query) started in this lane
+    if (src == 1u && gi < n_carry) {
+        // resume a suspended query: state, slot, then its aux stack into LDS
+        const WaveParams& K = karg<WaveParams>();
+        carry_rec(K.cq[K.parity], gi, K.carry_words).resume(q, slot, stk);
+        lds_put(L.H, cid, K.st.rec[2u * slot]);   // its pixel record, for its stay here
+        active = true;
+    } else if (src != 0u) {
+        // a fresh ray of the round, or a chain's next ray from the ray ring
+        F4 o, d, pre;
+        int pid;
+        if (src == 1u) {
+            const uint32_t fi = gi - n_carry;
+            o = FQ.ro[fi];
+            d = FQ.rd[fi];
+            pid = FQ.pid[fi];
+            pre = FQ.ri[fi];
+        } else {
+            o = lds_get(L.rq_ro, gi);
+            d = lds_get(L.rq_rd, gi);
+            pid = lds_get(L.rq_pid, gi);
+            pre = lds_get(L.rq_ri, gi);
+        }
+        Ray ray;
+        ray.o = mk3(o.x, o.y, o.z);
+        ray.d = mk3(d.x, d.y, d.z);
+        slot = f2u(o.w);
+        took = true;
+        pf.query_start();
+        q_init_pre(ray, d.w, pid, pre, q);
+        if (src == 1u) lds_put(L.H, cid, P.st.rec[2u * slot]);   // its pixel record, for its stay here
+        active = true;
+    }
+    if (src != 0u) q.cid = cid;
+    const uint32_t ntook = (uint32_t)__popcll(__ballot(took));
+    N.rays += ntook;
+    N.init_exact += (uint32_t)__popcll(__ballot(took && q.phase == Q_EXACT));
+}
+
+// One replay step kind per trip besides the aux steps (the kinds' code paths would
+// otherwise all be issued every trip): round-robin over the kinds present, from the one
+// after `rr`, the kind served last.  `kind` = this lane's (0 and 7: none).  0 = none present.
+__device__ __forceinline__ uint32_t path_pick_kind(uint32_t kind, uint32_t rr) {
+    uint32_t present = 0u;
+#pragma unroll
+    for (uint32_t k = 1; k <= PT_RKINDS; ++k)
+        if (__ballot(kind == k) != 0ull) present |= 1u << k;
+    uint32_t pick = 0u;
+#pragma unroll
+    for (uint32_t j = 1; j <= PT_RKINDS; ++j) {
+        const uint32_t c = (rr + j - 1u) % PT_RKINDS + 1u;
+        if (pick == 0u && ((present >> c) & 1u)) pick = c;
+    }
+    return pick;
+}
+// aux_extra more aux-node steps in the same trip for the lanes whose next step is one
+template <uint32_t STRIDE, class PF>
+__device__ __forceinline__ void path_aux_extra(const WaveParams& P, bool active, Query& q, QCounts& C, LdsMemN<STRIDE>& stk,
+                                               PF& pf) {
+#pragma unroll 1
+    for (uint32_t x = 0; x < P.aux_extra; ++x) {
+        const bool a2 = active && q.phase == Q_AUX && !(q.node & PT_LEAFQ);
+        if (__ballot(a2) == 0ull) break;
+        pf.extra_aux((uint32_t)__popcll(__ballot(a2)));
+        if (a2) q_aux_step(P.S, q, C, stk);
+    }
+}
+// Finished queries -> this wave's done ring wq, in lane order, as far as it has room
+// (the shade wave recomputes t, n and side from the prim); the others wait in their lanes
+// (phase Q_DONE) for the next trip.  dq_res = the ring's entries written and published.
+template <uint32_t NQ, class PF>
+__device__ __forceinline__ void path_retire(PathLds<NQ>& L, uint32_t wq, bool& active, uint32_t& slot, Query& q, uint32_t& dq_res,
+                                            uint32_t& fallbacks, PF& pf) {
+    const uint32_t room = PT_DQN - (dq_res - __builtin_amdgcn_readfirstlane(lds_read(L.dq_head[wq])));
+    const unsigned long long mfin = __ballot(active && q.phase == Q_DONE);
+    const uint32_t rank = lanes_below(mfin);
+    const bool fin = active && q.phase == Q_DONE && rank < room;
+    const uint32_t nfin = (uint32_t)__popcll(mfin) < room ? (uint32_t)__popcll(mfin) : room;
+    const uint32_t dq_at = dq_res;
+    dq_res += nfin;
+    fallbacks += (uint32_t)__popcll(__ballot(active && q.phase == Q_EXACT));
+    if (active) {
+        if (fin) {
+            const uint32_t j = wq * PT_DQN + (dq_at + rank) % PT_DQN;
+            lds_put(&L.dq_ro[0][0], j, F4{q.ray.o.x, q.ray.o.y, q.ray.o.z, u2f(slot)});
+            lds_put(&L.dq_rd[0][0], j,
+                    F4{q.ray.d.x, q.ray.d.y, q.ray.d.z, u2f(q.res_id < 0 ? 0xffffffffu : (uint32_t)q.res_id)});
+            lds_put(&L.dq_cid[0][0], j, (uint16_t)q.cid);
+            active = false;
+            pf.query_done();
+        } else if (q.phase == Q_EXACT) {
+            // rare: the exact stack DFS after this kernel; the chain leaves the workgroup
+            // (hand-off site HO_EXACT, counted with the fallbacks; PT_TUNE drop=exact)
+            const WaveParams& K = karg<WaveParams>();
+            if (K.drop != 1u + HO_EXACT) {
+                const uint32_t k = atomicAdd(K.ctl + PT_CTL_SET * (1u - K.parity) + C_EXACT, 1u);
+                K.ex.ro[k] = F4{q.ray.o.x, q.ray.o.y, q.ray.o.z, u2f(slot)};
+                K.ex.rd[k] = F4{q.ray.d.x, q.ray.d.y, q.ray.d.z, u2f(k)};
+                K.st.rec[2u * slot] = lds_get(L.H, (uint32_t)q.cid);   // (k_wshade shades it from HBM)
+            }
+            atomicAdd(&L.leaked, 1u);   // (its table entry stays taken for the round)
+            atomicSub(&L.resident, 1u);
+            active = false;
+        }
+    }
+    if (nfin) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        if (lane_id() == 0u) lds_write(L.dq_tail[wq], dq_res);
+    }
+}
+// the wave's counters to this XCD's statistics copy
+__device__ __forceinline__ void path_flush_counts(const WaveParams& P, const PathCounts& N) {
+    unsigned long long* ctr = ctr_copy(P.counters);
+    wave_add_u64(ctr + 1, N.C.nodes);
+    wave_add_u64(ctr + 2, N.C.ptests);
+    wave_add_u64(ctr + 5, N.C.aux);
+    if (lane_id() == 0u) {
+        if (N.rays) atomicAdd(ctr + 0, (unsigned long long)N.rays);
+        if (N.rays && P.S.n_planes) atomicAdd(ctr + 3, (unsigned long long)N.rays * P.S.n_planes);
+        if (N.fallbacks) atomicAdd(ctr + 6, (unsigned long long)N.fallbacks);
+        if (N.fallbacks) atomicAdd(ctr + CTR_HO + HO_EXACT, (unsigned long long)N.fallbacks);
+        if (N.init_exact) atomicAdd(ctr + 7, (unsigned long long)N.init_exact);
+    }
+}
+
+// Query wave wq of the workgroup (its done ring: wq)
+template <uint32_t NQ, bool SPARSE>
+__device__ __forceinline__ void path_query_wave(const WaveParams& P, PathLds<NQ>& L, uint32_t wq) {
+    LdsMemN<64u * NQ> stk{L.stk + 64u * wq + lane_id(), P.lstack, PT_LSTACK};
+    uint32_t* out = P.ctl + PT_CTL_SET * (1u - P.parity);
+    const PathWork W = path_work<NQ>(P);
+    const RayQ FQ = P.fq[P.parity];
     const uint32_t xcc = xcc_id();
     uint32_t xs = 0u;                 // XCD batch counters found empty
     uint32_t bbase = 0u, bleft = 0u;  // this wave's batch of the round's work not yet handed out
-    bool exhausted = false;
+    bool exhausted = false;           // the round's work is used up
+    uint32_t trip = 0u;
     uint32_t wpost = 0u;              // trips since the round's work ran out
     uint32_t deadline = 0u;           // the round's end (path_ticks mode; 0 = not read yet)
-    uint32_t trip = 0u;
     uint32_t ptrip = 0u;              // trips since the last probe turn
-    const uint32_t wq = qw;                 // this query wave's done ring
-    uint32_t rr = 0u;                       // replay step kind served last
-    uint32_t dq_res = 0u;                   // done-ring entries written and published
+    uint32_t rr = 0u;                 // replay step kind served last
+    uint32_t dq_res = 0u;             // done-ring entries written and published
     bool active = false;
     uint32_t slot = 0u;
     Query q;
-    QCounts C{0u, 0u, 0u, 0u};
-    // wave-level counters (scalar registers; per-lane ones would cost VGPRs)
-    // (the plane tests are rays x n_planes: every ray taken was plane-tested by its producer;
-    // exact-DFS hand-offs per wave and launch stay far below 2^32)
-    uint64_t rays = 0u;
-    uint32_t fallbacks = 0u, init_exact = 0u;
+    PathCounts N{QCounts{0u, 0u, 0u, 0u}, 0u, 0u, 0u};
+    constexpr uint32_t CMAX = PathLds<NQ>::CMAX;
     QProf pf;                         // (diagnostics builds only: PT_WPROF)
     for (;;) {
         const unsigned long long idle = __ballot(!active);
         const uint32_t nidle = (uint32_t)__popcll(idle);
         pf.trip(nidle, L, wq);
-        if (!exhausted && (++trip & 15u) == 0u) {
-            // A wave whose lanes stay busy with its workgroup's chains does not pull,
-            // so it would never find the round's work used up and would run its
-            // chains to the end of the pass: look at the 8 batch counters instead.
-            bool used = true;
-            if (lane_id() < 8u) {
-                const uint32_t h = __hip_atomic_load(out + C_HEADS + 32u * lane_id(), __ATOMIC_RELAXED,
-                                                     __HIP_MEMORY_SCOPE_AGENT);
-                used = (8ull * h + lane_id()) * bsz >= n_total;
-            }
-            exhausted = __ballot(!used) == 0ull;
-        }
+        if (!exhausted && (++trip & 15u) == 0u) exhausted = path_work_used(out, W);
         if (exhausted && bleft == 0u) {
             bool over;
-            if (budget == 0xffffffffu) {
-                over = false;
-            } else if (karg<WaveParams>().path_ticks) {
-                // One deadline for the whole round: the trip counts of workgroups with heavy
-                // and light chains differ, so a per-wave trip budget ends them at different
-                // times and the first ones out wait for the last (a round of a rank of 8:
-                // query waves tripping ~75 % of the round's span)
-                if (deadline == 0u) {
-                    uint32_t d = 0u;
-                    if (lane_id() == 0u) {
-                        const uint32_t want = ((uint32_t)__builtin_amdgcn_s_memrealtime() + karg<WaveParams>().path_ticks) | 1u;
-                        const uint32_t old = atomicCAS(out + C_DEADLINE, 0u, want);
-                        d = old ? old : want;
-                    }
-                    deadline = __builtin_amdgcn_readfirstlane(d);
-                }
-                over = (int32_t)((uint32_t)__builtin_amdgcn_s_memrealtime() - deadline) >= 0;
-            } else {
-                over = wpost >= budget;
-            }
+            path_round_over(W, out, wpost, deadline, over);
             if (over) {
-                // the round is over for this wave: suspend its running queries (hand-off site
-                // HO_SUSPEND; PT_TUNE drop=suspend loses them instead)
-                const WaveParams& K0 = karg<WaveParams>();
-                const bool drop = K0.drop == 1u + HO_SUSPEND;
-                if (active && !drop) {
-                    const WaveParams& K = karg<WaveParams>();
-                    const uint32_t k = wave_append(K.ctl + PT_CTL_SET * (1u - K.parity) + C_CARRY, true);
-                    uint32_t* w = K.cq[1u - K.parity] + (size_t)k * K.carry_words;
-                    *reinterpret_cast<Query*>(w) = q;
-                    uint32_t* tail = w + sizeof(Query) / 4u;
-                    tail[0] = slot;
-                    for (uint32_t j = 0; j < q.sp; ++j) tail[1u + j] = stk.get(j);
-                    K.st.rec[2u * slot] = lds_get(L.H, (uint32_t)q.cid);   // the chain leaves the workgroup
-                }
-                const uint32_t ns = (uint32_t)__popcll(__ballot(active));
-                if (lane_id() == 0u && ns) {
-                    atomicSub(&L.resident, ns);
-                    atomicAdd(ctr_copy(K0.counters) + CTR_HO + HO_SUSPEND, (unsigned long long)ns);
-                }
-                pf.exit_budget();
+                path_suspend(L, stk, active, slot, q, pf);
                 break;
             }
             if (nidle == 64u && lds_read(L.resident) == 0u) break;   // no chain left anywhere
@@ -291,45 +480,15 @@ __device__ __forceinline__ void path_query_wave(const WaveParams& P, PathLds<NQ>
                 given = take;
             }
             if (given < nidle) {
-                uint32_t h = 0u, take = 0u;
-                if (lane_id() == 0u) {
-                    for (;;) {
-                        h = lds_read(L.rq_head);
-                        const uint32_t t = lds_read(L.rq_tail), want = nidle - given;
-                        take = t - h < want ? t - h : want;
-                        if (take == 0u || atomicCAS(&L.rq_head, h, h + take) == h) break;
-                    }
-                }
-                h = __builtin_amdgcn_readfirstlane(h);
-                take = __builtin_amdgcn_readfirstlane(take);
+                uint32_t h;
+                const uint32_t take = path_ring_take(L, nidle - given, h);
                 if (!active && pos >= given && pos < given + take) { src = 2u; gi = (h + pos - given) % CMAX; }
                 given += take;
                 pf.ring(take);
             }
             while (given < nidle && !exhausted) {
-                uint32_t v = PT_NOWORK, cnt = 0u;
-                if (lane_id() == 0u) {
-                    if (atomicAdd(&L.resident, bsz) + bsz + lds_read(L.leaked) > P.path_cap) {
-                        atomicSub(&L.resident, bsz);   // workgroup full: its chains first
-                        v = PT_CAPPED;
-                    } else {
-                        while (xs < 8u) {
-                            const uint32_t y = (xcc + xs) & 7u;
-                            const uint64_t b = 8ull * atomicAdd(out + C_HEADS + 32u * y, 1u) + y;
-                            if (b * bsz < n_total) { v = (uint32_t)(b * bsz); break; }
-                            ++xs;
-                        }
-                        if (v == PT_NOWORK) {
-                            atomicSub(&L.resident, bsz);
-                        } else {
-                            cnt = n_total - v < bsz ? n_total - v : bsz;
-                            if (cnt < bsz) atomicSub(&L.resident, bsz - cnt);
-                        }
-                    }
-                }
-                v = __builtin_amdgcn_readfirstlane(v);
-                xs = __builtin_amdgcn_readfirstlane(xs);
-                cnt = __builtin_amdgcn_readfirstlane(cnt);
+                uint32_t cnt;
+                const uint32_t v = path_pull_batch(P, L, out, W, xcc, xs, cnt);
                 if (v == PT_CAPPED) break;
                 if (v == PT_NOWORK) { exhausted = true; break; }
                 bbase = v;
@@ -341,91 +500,23 @@ __device__ __forceinline__ void path_query_wave(const WaveParams& P, PathLds<NQ>
                 bleft -= take;
                 given += take;
             }
-            // chains joining the workgroup (src 1: the round's work) take a pixel-table
-            // entry from the free ring (there are enough: the entries taken never exceed
-            // resident + leaked <= path_cap <= CMAX); ray-ring chains bring theirs
-            const unsigned long long mjoin = __ballot(src == 1u);
-            uint32_t fh = 0u;
-            if (mjoin) {
-                if (lane_id() == 0u) fh = atomicAdd(&L.f_head, (uint32_t)__popcll(mjoin));
-                fh = __builtin_amdgcn_readfirstlane(fh);
-            }
-            if (src != 0u) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            uint32_t cid = 0u;
-            if (src == 1u) cid = lds_get(L.F, (fh + lanes_below(mjoin)) % CMAX);
-            if (src == 2u) cid = lds_get(L.rq_cid, gi);
-            if (src == 1u) {
-                const uint32_t* pin = karg<WaveParams>().pin;
-                if (pin) gi = pin[gi];   // (the early cooperative launch took the other items)
-            }
-            bool took = false;   // a fresh ray (not a resumed query) started in this lane
-            if (src == 1u && gi < n_carry) {
-                // resume a suspended query: state, slot, then its aux stack into LDS
-                const WaveParams& K = karg<WaveParams>();
-                const uint32_t* w = K.cq[K.parity] + (size_t)gi * K.carry_words;
-                q = *reinterpret_cast<const Query*>(w);
-                const uint32_t* tail = w + sizeof(Query) / 4u;
-                slot = tail[0];
-                for (uint32_t k = 0; k < q.sp; ++k) stk.set(k, tail[1u + k]);
-                lds_put(L.H, cid, K.st.rec[2u * slot]);   // its pixel record, for its stay here
-                active = true;
-            } else if (src != 0u) {
-                // a fresh ray of the round, or a chain's next ray from the ray ring
-                F4 o, d, pre;
-                int pid;
-                if (src == 1u) {
-                    const uint32_t fi = gi - n_carry;
-                    o = FQ.ro[fi];
-                    d = FQ.rd[fi];
-                    pid = FQ.pid[fi];
-                    pre = FQ.ri[fi];
-                } else {
-                    o = lds_get(L.rq_ro, gi);
-                    d = lds_get(L.rq_rd, gi);
-                    pid = lds_get(L.rq_pid, gi);
-                    pre = lds_get(L.rq_ri, gi);
-                }
-                Ray ray;
-                ray.o = mk3(o.x, o.y, o.z);
-                ray.d = mk3(d.x, d.y, d.z);
-                slot = f2u(o.w);
-                took = true;
-                pf.query_start();
-                q_init_pre(ray, d.w, pid, pre, q);
-                if (src == 1u) lds_put(L.H, cid, P.st.rec[2u * slot]);   // its pixel record, for its stay here
-                active = true;
-            }
-            if (src != 0u) q.cid = cid;
-            const uint32_t ntook = (uint32_t)__popcll(__ballot(took));
-            rays += ntook;
-            init_exact += (uint32_t)__popcll(__ballot(took && q.phase == Q_EXACT));
+            path_start_lane(P, L, FQ, W.n_carry, src, gi, stk, active, slot, q, N, pf);
         }
         if (__ballot(active) == 0ull) {
             pf.sleep();
-            __builtin_amdgcn_s_sleep(2);   // nothing to run: chains are being shaded (no `continue`:
-        }                                  // a second back edge costs ~30 VGPRs)
+            __builtin_amdgcn_s_sleep(2);   // nothing to run: chains are being shaded
+        }
         pf.refill_end(active);
         if constexpr (SPARSE) {
 #pragma unroll 1
             for (uint32_t it = 0; it < P.sparse_steps; ++it) {
                 const bool run = active && (q.phase == Q_AUX || q.phase == Q_REPLAY);
                 if (__ballot(run) == 0ull) break;
-                if (run) q_step(P.S, q, C, stk);
+                if (run) q_step(P.S, q, N.C, stk);
             }
         } else {
-            // One replay step kind per trip besides the aux steps (the kinds' code paths
-            // would otherwise all be issued every trip): round-robin over the kinds present.
             uint32_t kind = active && q.phase == Q_REPLAY ? 1u + q.walk : active && q.phase == Q_AUX ? 0u : 7u;
-            uint32_t present = 0u;
-#pragma unroll
-            for (uint32_t k = 1; k <= PT_RKINDS; ++k)
-                if (__ballot(kind == k) != 0ull) present |= 1u << k;
-            uint32_t pick = 0u;
-#pragma unroll
-            for (uint32_t j = 1; j <= PT_RKINDS; ++j) {
-                const uint32_t c = (rr + j - 1u) % PT_RKINDS + 1u;
-                if (pick == 0u && ((present >> c) & 1u)) pick = c;
-            }
+            const uint32_t pick = path_pick_kind(kind, rr);
             if (pick) rr = pick;
             // candidate probes (the aux pass's leaf steps) run on every probe_every-th trip,
             // or whenever probe_min lanes wait for one: the probe code is issued for the
@@ -437,74 +528,20 @@ __device__ __forceinline__ void path_query_wave(const WaveParams& P, PathLds<NQ>
             if (want_probe && !probe_go) kind = 7u;
             pf.kinds(kind == 0u, pick != 0u, kind == 0u || kind == pick);
             pf.kind_mix(kind == 0u ? ((q.node & PT_LEAFQ) ? 1u : 0u) : kind == pick ? kind + 1u : 7u);
-            if (kind == 0u || kind == pick) q_step(P.S, q, C, stk);
-            // aux_extra more aux-node steps in the same trip for the lanes whose next step is one
-#pragma unroll 1
-            for (uint32_t x = 0; x < P.aux_extra; ++x) {
-                const bool a2 = active && q.phase == Q_AUX && !(q.node & PT_LEAFQ);
-                if (__ballot(a2) == 0ull) break;
-                pf.extra_aux((uint32_t)__popcll(__ballot(a2)));
-                if (a2) q_aux_step(P.S, q, C, stk);
-            }
+            if (kind == 0u || kind == pick) q_step(P.S, q, N.C, stk);
+            path_aux_extra(P, active, q, N.C, stk, pf);
         }
         pf.step_end();
-        // finished queries -> this wave's done ring, in lane order, as far as it has room
-        // (the shade wave recomputes t, n and side from the prim); the others wait in
-        // their lanes (phase Q_DONE) for the next trip
-        const uint32_t room = PT_DQN - (dq_res - __builtin_amdgcn_readfirstlane(lds_read(L.dq_head[wq])));
-        const unsigned long long mfin = __ballot(active && q.phase == Q_DONE);
-        const uint32_t rank = lanes_below(mfin);
-        const bool fin = active && q.phase == Q_DONE && rank < room;
-        const uint32_t nfin = (uint32_t)__popcll(mfin) < room ? (uint32_t)__popcll(mfin) : room;
-        const uint32_t dq_at = dq_res;
-        dq_res += nfin;
-        fallbacks += (uint32_t)__popcll(__ballot(active && q.phase == Q_EXACT));
-        if (active) {
-            if (fin) {
-                const uint32_t j = wq * PT_DQN + (dq_at + rank) % PT_DQN;
-                lds_put(&L.dq_ro[0][0], j, F4{q.ray.o.x, q.ray.o.y, q.ray.o.z, u2f(slot)});
-                lds_put(&L.dq_rd[0][0], j,
-                        F4{q.ray.d.x, q.ray.d.y, q.ray.d.z, u2f(q.res_id < 0 ? 0xffffffffu : (uint32_t)q.res_id)});
-                lds_put(&L.dq_cid[0][0], j, (uint16_t)q.cid);
-                active = false;
-                pf.query_done();
-            } else if (q.phase == Q_EXACT) {
-                // rare: the exact stack DFS after this kernel; the chain leaves the workgroup
-                // (hand-off site HO_EXACT, counted with the fallbacks; PT_TUNE drop=exact)
-                const WaveParams& K = karg<WaveParams>();
-                if (K.drop != 1u + HO_EXACT) {
-                    const uint32_t k = atomicAdd(K.ctl + PT_CTL_SET * (1u - K.parity) + C_EXACT, 1u);
-                    K.ex.ro[k] = F4{q.ray.o.x, q.ray.o.y, q.ray.o.z, u2f(slot)};
-                    K.ex.rd[k] = F4{q.ray.d.x, q.ray.d.y, q.ray.d.z, u2f(k)};
-                    K.st.rec[2u * slot] = lds_get(L.H, (uint32_t)q.cid);   // (k_wshade shades it from HBM)
-                }
-                atomicAdd(&L.leaked, 1u);   // (its table entry stays taken for the round)
-                atomicSub(&L.resident, 1u);
-                active = false;
-            }
-        }
-        if (nfin) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            if (lane_id() == 0u) lds_write(L.dq_tail[wq], dq_res);
-        }
+        path_retire(L, wq, active, slot, q, dq_res, N.fallbacks, pf);
         pf.done_end();
     }
-    unsigned long long* ctr = ctr_copy(P.counters);
-    wave_add_u64(ctr + 1, C.nodes);
-    wave_add_u64(ctr + 2, C.ptests);
-    wave_add_u64(ctr + 5, C.aux);
-    if (lane_id() == 0u) {
-        if (rays) atomicAdd(ctr + 0, (unsigned long long)rays);
-        if (rays && P.S.n_planes) atomicAdd(ctr + 3, (unsigned long long)rays * P.S.n_planes);
-        if (fallbacks) atomicAdd(ctr + 6, (unsigned long long)fallbacks);
-        if (fallbacks) atomicAdd(ctr + CTR_HO + HO_EXACT, (unsigned long long)fallbacks);
-        if (init_exact) atomicAdd(ctr + 7, (unsigned long long)init_exact);
-    }
-    pf.store(P.wg_prof, rays);
+    path_flush_counts(P, N);
+    pf.store(P.wg_prof, N.rays);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     if (lane_id() == 0u) atomicAdd(&L.qw_done, 1u);
 }
 
+// ---- the shade wave ------------------------------------------------------------
 template <uint32_t NQ>
 __device__ __forceinline__ void path_shade_wave(const WaveParams& P, PathLds<NQ>& L) {
     constexpr uint32_t CMAX = PathLds<NQ>::CMAX;
@@ -524,8 +561,7 @@ __device__ __forceinline__ void path_shade_wave(const WaveParams& P, PathLds<NQ>
     if (karg<WaveParams>().side_flags & PT_SHADE_HOLD) {
         // (test hook: the query waves of a round with a budget leave by themselves)
         const WaveParams& K = karg<WaveParams>();
-        const uint32_t* in = K.ctl + PT_CTL_SET * K.parity;
-        const uint32_t n_total = K.pin ? K.pin_n : in[C_FRESH] + in[C_CARRY];
+        const uint32_t n_total = path_work<NQ>(K).n_total;
         if (n_total > K.path_runend)
             while (__builtin_amdgcn_readfirstlane(lds_read(L.qw_done)) != NQ) __builtin_amdgcn_s_sleep(2);
     }
@@ -698,6 +734,28 @@ __device__ __forceinline__ void path_shade_wave(const WaveParams& P, PathLds<NQ>
     }
 }
 
+// the workgroup's LDS at the kernel's start (before its barrier)
+template <uint32_t NQ>
+__device__ __forceinline__ void path_lds_init(const WaveParams& P, PathLds<NQ>& L) {
+    // the first planes and emitters (the shade wave's plane tests and light sampling)
+    const uint32_t npl = (P.S.n_planes < QC_NPL ? P.S.n_planes : QC_NPL) * 5u;
+    const uint32_t nem = (P.S.n_emitters < QC_NEM ? P.S.n_emitters : QC_NEM) * 5u;
+    for (uint32_t i = threadIdx.x; i < npl; i += blockDim.x) {
+        const uint32_t pi = P.S.planes[i / 5u];
+        F4 v = reinterpret_cast<const F4*>(P.S.prims + pi)[i % 5u];
+        if (i % 5u == 2u) v.w = u2f(pi);
+        lds_put(L.pl, i, v);
+    }
+    for (uint32_t i = threadIdx.x; i < nem; i += blockDim.x)
+        lds_put(L.em, i, reinterpret_cast<const F4*>(P.S.prims + P.S.emitters[i / 5u])[i % 5u]);
+    // the rings empty, every pixel-table entry free
+    if (threadIdx.x == 0u) {
+        L.rq_head = L.rq_tail = L.resident = L.qw_done = L.leaked = L.f_head = 0u;
+    }
+    if (threadIdx.x < NQ) L.dq_tail[threadIdx.x] = L.dq_head[threadIdx.x] = 0u;
+    for (uint32_t i = threadIdx.x; i < PathLds<NQ>::CMAX; i += blockDim.x) lds_put(L.F, i, (uint16_t)i);
+}
+
 // The end-of-pass (sparse) kernel runs few chains, bound by their latency, not by
 // occupancy: it is held to 2 waves per SIMD (256 VGPRs, no spills; 2 workgroups per CU
 // run at a time, the grid's others start as those finish and find the round's work taken)
@@ -706,24 +764,7 @@ __global__ void __launch_bounds__(64u * (NQ + 1u))
 __attribute__((amdgpu_waves_per_eu(SPARSE ? 2u : PT_PATH_WAVES_PER_EU, SPARSE ? 2u : PT_PATH_WAVES_PER_EU)))
 k_wpath(WaveParams P) {
     __shared__ PathLds<NQ> L;
-    {
-        // the first planes and emitters (the shade wave's plane tests and light sampling)
-        const uint32_t npl = (P.S.n_planes < QC_NPL ? P.S.n_planes : QC_NPL) * 5u;
-        const uint32_t nem = (P.S.n_emitters < QC_NEM ? P.S.n_emitters : QC_NEM) * 5u;
-        for (uint32_t i = threadIdx.x; i < npl; i += blockDim.x) {
-            const uint32_t pi = P.S.planes[i / 5u];
-            F4 v = reinterpret_cast<const F4*>(P.S.prims + pi)[i % 5u];
-            if (i % 5u == 2u) v.w = u2f(pi);
-            lds_put(L.pl, i, v);
-        }
-        for (uint32_t i = threadIdx.x; i < nem; i += blockDim.x)
-            lds_put(L.em, i, reinterpret_cast<const F4*>(P.S.prims + P.S.emitters[i / 5u])[i % 5u]);
-    }
-    if (threadIdx.x == 0u) {
-        L.rq_head = L.rq_tail = L.resident = L.qw_done = L.leaked = L.f_head = 0u;
-    }
-    if (threadIdx.x < NQ) L.dq_tail[threadIdx.x] = L.dq_head[threadIdx.x] = 0u;
-    for (uint32_t i = threadIdx.x; i < PathLds<NQ>::CMAX; i += blockDim.x) lds_put(L.F, i, (uint16_t)i);   // every entry free
+    path_lds_init(P, L);
     wprof_start(P.wg_prof);
     __syncthreads();
     // waves 0 .. NQ-1 query, wave NQ shades

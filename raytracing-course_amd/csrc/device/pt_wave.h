@@ -47,12 +47,10 @@ __device__ __forceinline__ void push_ray(const WaveParams& P, const RayQ& Q, uin
     Q.ri[qi] = q_prep(P.S, ray);
 }
 
-// The pixel slot of a round's work item gi: carry record gi (a suspended Query, then its
-// slot word) below n_carry, else fresh ray gi - n_carry (its slot in ro.w)
-__device__ __forceinline__ uint32_t carry_slot(const uint32_t* rec) { return rec[sizeof(Query) / 4u]; }
+// The pixel slot of a round's work item gi: carry record gi (pt_kernels.h CarryRec) below
+// n_carry, else fresh ray gi - n_carry (its slot in ro.w)
 __device__ __forceinline__ uint32_t work_item_slot(const WaveParams& P, uint32_t gi, uint32_t n_carry) {
-    return gi < n_carry ? carry_slot(P.cq[P.parity] + (size_t)gi * P.carry_words)
-                        : f2u(P.fq[P.parity].ro[gi - n_carry].w);
+    return gi < n_carry ? carry_rec(P.cq[P.parity], gi, P.carry_words).slot() : f2u(P.fq[P.parity].ro[gi - n_carry].w);
 }
 
 // A value the optimiser must treat as new at this point: a loop-invariant expression
@@ -83,23 +81,21 @@ __device__ __forceinline__ Ray camera_sample(const CamView& cam, Rng& R, uint32_
     return camera_ray(cam, fx, fy);
 }
 
-// One finished query of a pixel's chain (src/scene.cpp:91-177 for the vertex,
-// :198 for the fold): the vertex and its fold record -- or the miss -- and, at
-// path end, the backward fold into the pixel sum.  Returns true with `ray` set
-// to the chain's next ray (the child, or the next sample's camera ray); false
-// when the pixel has reached this pass's target.  `ray` enters as the query ray.
-// `sdone` returns whether a sample of the pixel ended here.
+// One finished query of a pixel's chain in two steps, the pixel record `hot` (RNG, vertex
+// count, samples done) in registers -- wherever it lives: HBM (shade_item, for k_wshade) or
+// a path workgroup's LDS table (pt_path.hip vertex_item / end_item).  A pixel has one
+// chain, and its next sample starts only from end_step, so its operations keep their order.
+// vertex_step: the vertex (src/scene.cpp:91-177) and its fold record; true with `ray` (which
+// enters as the query ray) = the child ray, or false when the path ended -- the miss, or the
+// vertex ends it --, `miss` telling how.
 template <class EM>
-__device__ __forceinline__ bool shade_item(const WaveParams& P, const EM& em, uint32_t slot, Ray& ray, uint32_t hid,
-                                           bool& sdone) {
-    bool emit = false;
-    PixelHot hot = load_hot(P.st, slot);     // one 16-B load: RNG, vertex count, samples done
+__device__ __forceinline__ bool vertex_step(const WaveParams& P, const EM& em, PixelHot& hot, uint32_t slot, Ray& ray,
+                                            uint32_t hid, bool& miss) {
     uint32_t nv = hot.nv;
-    uint32_t end = PE_LIVE;
     Rng R = hot.R;
-    if (hid == 0xffffffffu) {
-        end = PE_MISS;
-    } else {
+    bool live = false;
+    miss = hid == 0xffffffffu;
+    if (!miss) {
         // the closest hit's t, normal and side: recomputed from its primitive
         // (the query's own test, same operations -> same bits)
         Hit h;
@@ -110,32 +106,46 @@ __device__ __forceinline__ bool shade_item(const WaveParams& P, const EM& em, ui
         HbmVStore vs = fold_store(P.st, slot);
         vs.put(nv, idm, s1, s2);
         ++nv;
-        if (!cont) end = PE_TERM;
-        else if (nv >= P.depth) end = PE_CUT;   // RayTrace(.., 0) = 0
-        else emit = true;
-    }
-    sdone = end != PE_LIVE;
-    if (end != PE_LIVE) {
-        // path over: backward fold (deepest vertex first), src/scene.cpp:198 sum += ...
-        uint32_t pix;
-        const f3 sum = fold_path(P.st, P.S.shade, slot, nv, end == PE_MISS ? P.S.bg : mk3(0.f, 0.f, 0.f), pix);
-        store_sum(P.st, slot, sum, pix);
-        const uint32_t done = hot.done + 1u;
-        hot.done = done;
-        nv = 0u;
-        if (done < P.target) {
-            // the pixel's next sample: jitter draws + camera ray
-            const WaveParams& K = karg<WaveParams>();   // (read here: see end_item)
-            ray = camera_sample(K.cam, R, pix % K.tm.W, pix / K.tm.W);
-            emit = true;
-        }
+        live = cont && nv < P.depth;   // RayTrace(.., 0) = 0
     }
     hot.nv = nv;
     hot.R = R;
-    store_hot(P.st, slot, hot);               // one 16-B store
+    return live;
+}
+// end_step: an ended path's backward fold into the pixel sum (deepest vertex first,
+// src/scene.cpp:198 sum += ...) and the next sample's jitter draws and camera ray; false =
+// the pixel has reached this pass's target.
+__device__ __forceinline__ bool end_step(const WaveParams& P, PixelHot& hot, uint32_t slot, bool miss, Ray& ray) {
+    Rng R = hot.R;
+    uint32_t pix;
+    const f3 sum = fold_path(P.st, P.S.shade, slot, hot.nv, miss ? P.S.bg : mk3(0.f, 0.f, 0.f), pix);
+    store_sum(P.st, slot, sum, pix);
+    hot.done += 1u;
+    hot.nv = 0u;
+    bool emit = false;
+    if (hot.done < P.target) {
+        // (the camera block read here, not held in SGPRs across a persistent loop)
+        const WaveParams& K = karg<WaveParams>();
+        ray = camera_sample(K.cam, R, pix % K.tm.W, pix / K.tm.W);
+        emit = true;
+    }
+    hot.R = R;
     return emit;
 }
-
+// Both for a record in HBM: one 16-B load, one 16-B store.  Returns true with `ray` set to
+// the chain's next ray (the child, or the next sample's camera ray); `sdone` returns
+// whether a sample of the pixel ended here.
+template <class EM>
+__device__ __forceinline__ bool shade_item(const WaveParams& P, const EM& em, uint32_t slot, Ray& ray, uint32_t hid,
+                                           bool& sdone) {
+    PixelHot hot = load_hot(P.st, slot);
+    bool miss;
+    bool emit = vertex_step(P, em, hot, slot, ray, hid, miss);
+    sdone = !emit;
+    if (sdone) emit = end_step(P, hot, slot, miss, ray);
+    store_hot(P.st, slot, hot);
+    return emit;
+}
 
 #define PT_SUSPENDED 0xfffffffeu   // done.id of a query suspended to the next round
 

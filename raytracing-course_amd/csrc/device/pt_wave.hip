@@ -143,10 +143,8 @@ __global__ void __launch_bounds__(256) k_side_take(WaveParams P, uint32_t k, Ray
     const uint32_t kc = wave_append(side_ctl + C_CARRY, carry);
     const uint32_t kf = wave_append(side_ctl + C_FRESH, keep && !carry);
     if (carry) {
-        const uint32_t* w = P.cq[P.parity] + (size_t)gi * P.carry_words;
-        uint32_t* d = side_carry + (size_t)kc * P.carry_words;
-        *reinterpret_cast<Ray*>(d) = reinterpret_cast<const Query*>(w)->ray;
-        d[sizeof(Query) / 4u] = carry_slot(w);
+        const auto rec = carry_rec(P.cq[P.parity], gi, P.carry_words);
+        carry_put_restart(carry_rec(side_carry, kc, P.carry_words), rec.ray(), rec.slot());
     } else if (keep) {
         const RayQ& F = P.fq[P.parity];
         const uint32_t fi = gi - n_carry;

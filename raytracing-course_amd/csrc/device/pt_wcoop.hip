@@ -19,10 +19,9 @@ namespace pt {
 enum : uint32_t { QH_IDX = 0u, QH_T, QH_LID, QH_NX, QH_NY, QH_NZ, QH_IN, QH_INFO, QH_N };
 template <uint32_t T>
 struct QcTeamLds {
-    // aux stack words per chain (also the leader's exact DFS stack): a whole-wave team's own;
-    // smaller teams share their wave's pool (QcPoolLds), SCAP words per chain
-    // (teams of 4: 64, so that their wave's pool -- 16 chains -- stays at 1,024 words)
-    static constexpr uint32_t SCAP = T == 64u ? 448u : T == 32u ? 192u : T == 4u ? 64u : QC_SCAP_MIN;
+    // aux stack words per chain (pt_kernels.h): a whole-wave team's own stack; smaller teams
+    // share their wave's pool (QcPoolLds), SCAP words per chain
+    static constexpr uint32_t SCAP = qc_stack_words(T);
     static constexpr uint32_t CCAP = 5u * T;                    // candidates (< T + 4 T at any time)
     static constexpr uint32_t HCAP = T >= 32u ? 32u : T == 16u ? 16u : T == 8u ? 12u : 8u;   // hitting leaves per
                                     // query (more: the exact DFS); LDS fits 3 WGs per CU (teams of 4: 2)
@@ -42,9 +41,9 @@ struct QcTeamLds {
 template <uint32_t T>
 struct QcPoolLds {
     static constexpr uint32_t CPW = 64u / T;                    // chains per wave
-    static constexpr uint32_t SH = CPW > 8u ? 28u : 29u;        // item = chain << SH | node (host: nodes < 2^SH)
+    static constexpr uint32_t SH = qc_item_shift(T);            // item = chain << SH | node (host: nodes < 2^SH)
     static constexpr uint32_t MASK = (1u << SH) - 1u;
-    static constexpr uint32_t SW = QcTeamLds<T>::SCAP * CPW;    // pending nodes (chain c's exact DFS stack after
+    static constexpr uint32_t SW = qc_pool_words(T);            // pending nodes (chain c's exact DFS stack after
                                                                 // the query: words [c SCAP, (c + 1) SCAP))
     static constexpr uint32_t CW = 128u;                        // candidates (< 64 + 64 at any time)
     uint32_t stk[SW];
@@ -568,7 +567,7 @@ __device__ __forceinline__ bool coop_shade(const WaveParams& P, const QcScene& Q
         px.done += 1u;
         px.nv = 0u;
         if (px.done < P.target) {
-            const WaveParams& K = karg<WaveParams>();   // (read here: see end_item)
+            const WaveParams& K = karg<WaveParams>();   // (read here: see end_step)
             ray = camera_sample(K.cam, px.R, sp.w % K.tm.W, sp.w / K.tm.W);
             emit = true;
         }
@@ -585,9 +584,9 @@ __device__ __forceinline__ bool coop_item(const WaveParams& P, const QcScene& Q,
     if (gi < n_carry) {
         // a query suspended by the path engine: restarted from its ray (a query is a
         // function of the ray alone; its ray and plane tests were counted when taken)
-        const uint32_t* w = P.cq[P.parity] + (size_t)gi * P.carry_words;
-        ray = reinterpret_cast<const Query*>(w)->ray;
-        slot = carry_slot(w);
+        const auto rec = carry_rec(P.cq[P.parity], gi, P.carry_words);
+        ray = rec.ray();
+        slot = rec.slot();
         q_planes_e(P.S, PlanesLds<BIG>{Q, P.S}, ray, Pt, pid);
         pre = q_prep(P.S, ray);
         return false;
@@ -617,9 +616,7 @@ __device__ __forceinline__ void coop_restart(const WaveParams& P, uint32_t k, co
                                              uint32_t slot) {
     Query q;
     q_init_pre(ray, Pt, pid, pre, q);
-    uint32_t* w = P.yield_cq + (size_t)k * P.carry_words;
-    *reinterpret_cast<Query*>(w) = q;
-    w[sizeof(Query) / 4u] = slot;
+    carry_put_restart(carry_rec(P.yield_cq, k, P.carry_words), q, slot);
 }
 // The wave's work counters (LDS, lane 0) to this XCD's statistics copy, and zeroed: each
 // to its total and to this engine's share (pt_stats coop_*; 0 = none).  The parameter

@@ -223,7 +223,7 @@ int check_dups(pt_session* ss, const pt::WaveParams& wp, uint32_t p, uint32_t ch
         if (seen[slot]++) ++dup;
     };
     for (uint32_t i = 0; i < nf; ++i) see(pt::f2u(ro[i].w));
-    for (uint32_t i = 0; i < nc; ++i) see(cw[(size_t)i * ss->carry_words + sizeof(pt::Query) / 4]);
+    for (uint32_t i = 0; i < nc; ++i) see(pt::carry_rec(cw.data(), i, ss->carry_words).slot());
     if (dup || bad)
         fprintf(stderr, "dupcheck: round %u (%s%s) fresh %u carry %u: %u duplicate slot(s), %u out of range\n",
                 ss->rounds, chains < ss->lowq ? "low" : "full", side ? "+side" : "", nf, nc, dup, bad);

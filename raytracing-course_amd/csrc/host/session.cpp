@@ -210,7 +210,7 @@ int pt_session_create(pt_scene* s, const pt_session_opts* o, pt_session** out) {
         ss->full_grid = cus * (uint32_t)std::max(1, tune_int("wg_per_cu", (int)pt::path_wg_per_cu(ss->full_nq)));
         // the query lanes of the larger launch
         const uint64_t lanes = std::max<uint64_t>((uint64_t)ss->path_grid * PT_NQ_BASE, (uint64_t)ss->full_grid * ss->full_nq) * 64u;
-        // suspended-query records: Query | slot | aux stack, rounded to 16 B.  Only a
+        // suspended-query records (pt_kernels.h CarryRec: Query | slot | aux stack).  Only a
         // query lane suspends (one query at round end), and a pixel has at most one ray
         // in flight, so a round appends at most min(pixels, query lanes) of them: the
         // carry queue can never overflow.  The exact-DFS hand-over queues (ex, done, hid)
@@ -218,7 +218,7 @@ int pt_session_create(pt_scene* s, const pt_session_opts* o, pt_session** out) {
         // chain of the round's supply, so a round can hand over a ray of every chain --
         // at most one per pixel (a chain that leaves for k_wexact leaves the round).
         // They hold n entries.
-        ss->carry_words = ((uint32_t)(sizeof(pt::Query) / 4) + 1u + std::max<uint32_t>(s->auxw_stack, 1u) + 3u) & ~3u;
+        ss->carry_words = pt::carry_record_words(std::max<uint32_t>(s->auxw_stack, 1u));
         ss->lane_cap = (uint32_t)std::min<uint64_t>(n, lanes);
         ss->carry_cap = ss->lane_cap;
         // a round whose chains are this few runs them to the end of the pass (a few
@@ -241,16 +241,15 @@ int pt_session_create(pt_scene* s, const pt_session_opts* o, pt_session** out) {
         ss->coop_grid = cus * 8u;
         // (a depth-first descent below the expansion limit adds at most 3 entries per level)
         const uint32_t reserve = 3u * (s->auxsl_depth + 2u);
-        // a team size's stacks hold this tree: the expansion (its own stack, or for teams of 4
-        // the wave's pool of 1,024 words) a depth-first descent below the reserve, and the
-        // leader's exact DFS (its stack, or its 64-word slice of the pool) the whole tree
-        // (and for teams below 64 the pool's items, chain << 29 | node -- teams of 4: << 28 -- hold
+        // a team size's stacks hold this tree (the engine's capacities: pt_kernels.h qc_*): the
+        // expansion (its own stack, or for teams of 4 the wave's pool) a depth-first descent
+        // below the reserve, and the leader's exact DFS (its stack, or its slice of the pool)
+        // the whole tree (and for teams below 64 the pool's items, chain << shift | node, hold
         // every aux entry index)
+        auto stack_ok = [&](uint32_t expand, uint32_t dfs) { return expand >= reserve + 64u && s->max_stack <= dfs; };
         auto team_ok = [&](uint32_t t) {
-            if (t < 64u && s->auxsl.size() >= (1ull << (t == 4u ? 28 : 29))) return false;
-            if (t == 4u) return 1024u >= reserve + 64u && s->max_stack <= 64u;
-            const uint32_t scap = t == 64u ? 448u : t == 32u ? 192u : QC_SCAP_MIN;
-            return scap >= reserve + 64u && s->max_stack <= scap;
+            if (t < 64u && s->auxsl.size() >= (1ull << pt::qc_item_shift(t))) return false;
+            return stack_ok(t == 4u ? pt::qc_pool_words(t) : pt::qc_stack_words(t), pt::qc_stack_words(t));
         };
         ss->coop_team = (uint32_t)tune_int("coop_team", (int)ss->coop_team);
         if (ss->coop_team != 4u && ss->coop_team != 8u && ss->coop_team != 16u && ss->coop_team != 32u)
@@ -258,7 +257,7 @@ int pt_session_create(pt_scene* s, const pt_session_opts* o, pt_session** out) {
         if (!team_ok(ss->coop_team)) ss->coop_team = 64u;   // deep trees: whole-wave teams
         // (paths deeper than QC_FOLD keep their further fold records in HBM, planes and
         // emitters beyond QC_NPL / QC_NEM come from HBM: no scene limit besides the stacks)
-        if (448u < reserve + 64u || s->max_stack > 448u)
+        if (!stack_ok(pt::qc_stack_words(64u), pt::qc_stack_words(64u)))
             ss->coop_max = 0;
         else ss->coop_reserve = reserve;
         // with the cooperative engine the path engine never runs a round to the end:
@@ -278,7 +277,7 @@ int pt_session_create(pt_scene* s, const pt_session_opts* o, pt_session** out) {
         // ... and, before that, its last coop_grow_mid chains to teams of 32 (0: no such stage; a
         // tree too deep for the teams-of-32 stack skips it)
         ss->coop_grow_mid = (uint32_t)std::max(0, tune_int("coop_grow_mid", 0));
-        if (192u < reserve + 64u || s->max_stack > 192u) ss->coop_grow_mid = 0u;
+        if (!stack_ok(pt::qc_stack_words(32u), pt::qc_stack_words(32u))) ss->coop_grow_mid = 0u;
         // Early cooperative launch (teams of side_team lanes, QC_WAVES waves per workgroup):
         // the low-chain rounds leave each CU room for one more workgroup, which the heaviest
         // chains use from then on instead of waiting for the final hand-over
