@@ -237,6 +237,33 @@ int pt_session_stats(pt_session* ss, pt_stats* st);
 void* pt_session_stream(pt_session* ss);
 void pt_session_free(pt_session* ss);
 
+/* ------------------------------------------------------------ ray queries
+ * Scene::RayIntersection (src/scene.cpp:46-77) for the caller's own rays, bit for bit: the
+ * planes, then the reference BVH with its pruning semantics (first-hit buffers, picking,
+ * visibility passes).  No reference counterpart as an interface: RayIntersection is private
+ * to the reference's render.  A ray is used as given (never normalised).  A hit's id is the
+ * primitive's index in the prepared order -- the order of pt_scene_dump_bvh's primitives,
+ * planes at the end; a miss is id = -1 with the other five words 0. */
+typedef struct pt_rayq pt_rayq;
+typedef struct pt_ray     { float o[3], d[3]; } pt_ray;
+typedef struct pt_ray_hit { int32_t id; float t; float n[3]; uint32_t interior; } pt_ray_hit;
+
+/* a ray-query context on `device` for runs of up to max_rays (1 .. 2^32 - 1) rays; prepares
+ * the scene if needed; the scene must outlive the context */
+int pt_rayq_create(pt_scene* s, int device, uint64_t max_rays, pt_rayq** out);
+/* asynchronous on `stream` (a hipStream_t; NULL = the null stream); dev_rays / dev_hits are
+ * device pointers on the context's device; n <= max_rays; n = 0 enqueues nothing.  One run at
+ * a time per context: a run first waits (on the host) for the context's previous run. */
+int pt_rayq_run(pt_rayq* q, void* stream, uint64_t n, const pt_ray* dev_rays, pt_ray_hit* dev_hits);
+/* waits for the last run; fills rays, node_visits, prim_tests, plane_tests, aux_visits,
+ * fallbacks, fallbacks_ray, errors (must be 0), kernel_ms and the *_bytes record sizes for the
+ * runs since the last call */
+int pt_rayq_stats(pt_rayq* q, pt_stats* st);
+void pt_rayq_free(pt_rayq* q);
+/* convenience, host pointers: uploads, runs, downloads, in chunks of at most 2^22 rays so that
+ * device memory stays bounded; synchronous; stats may be NULL */
+int pt_intersect(pt_scene* s, int device, uint64_t n, const pt_ray* rays, pt_ray_hit* hits, pt_stats* stats);
+
 const char* pt_last_error(void);
 int pt_abi_version(void);
 

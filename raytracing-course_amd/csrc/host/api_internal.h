@@ -8,6 +8,7 @@
 //   session.cpp   tile sessions: set-up, the megakernel pass, resolve, stats (pt_session_*)
 //   rounds.cpp    the wavefront pass: path rounds, early / final cooperative launches
 //   render.cpp    Scene::Render equivalent: per-GPU threads, the RCCL / host gather, PPM
+//   rayq.cpp      the ray-query engine: closest-hit queries for the caller's rays (pt_rayq_*, pt_intersect)
 //   selftest.cpp  host execution of the device query / integrator code (tests only)
 #pragma once
 #include "pt.h"
@@ -30,6 +31,7 @@
 
 #include "../device/pt_coop.h"
 #include "../device/pt_kernels.h"
+#include "../device/pt_rays.h"
 #include "pt_scene.h"
 
 #pragma GCC visibility push(hidden)
@@ -137,6 +139,7 @@ hipError_t read_counters(pt_session* ss, unsigned long long c[PT_CTR_STRIDE]);
 int flush_trace(pt_session* ss);
 int trace_wave(pt_session* ss, uint32_t spp);
 pt::SceneView device_view(const pt_session* ss);
+pt::SceneView device_view(const pt_scene* s, const DevScene& ds);   // ... of any device copy (rayq.cpp)
 // the hand-off site named `name` (PT_HO_*: "suspend", "flush", "ringout", "exact", "side_take",
 // "side_yield", "side_handon", "grow_yield", "grow_handon"), or -1
 int handoff_site(const char* name);
@@ -277,6 +280,21 @@ struct pt_session {
     unsigned long long* prog_dev = nullptr;
     pt::CamView cam{};
     int traversal = PT_TRAVERSAL_REPLAY;
+};
+
+// A ray-query context (rayq.cpp): the scene's copy on one device and the run state of k_rays.
+struct pt_rayq {
+    pt_scene* sc = nullptr;
+    int dev = 0;
+    uint64_t max_rays = 0;
+    pt::RaysParams p{};             // the view of the device copy and the arena's pieces (rays, hits, n, batch: per run)
+    // one allocation: the control block | the statistics counters | the exact list (max_rays words)
+    unsigned char* arena = nullptr;
+    uint32_t block = 256, max_grid = 1;   // k_rays' workgroup (its lanes' stacks fit the LDS) and the resident grid
+    hipEvent_t e0 = nullptr, e1 = nullptr;   // around the last run's kernels
+    bool pending = false;           // ... whose time has not been added to kernel_ms yet
+    double kernel_ms = 0.0;         // since the last pt_rayq_stats
+    unsigned long long seen[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the counters at the last pt_rayq_stats
 };
 
 #pragma GCC visibility pop

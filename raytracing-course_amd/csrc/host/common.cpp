@@ -110,6 +110,8 @@ const Rccl& rccl() {
 //   batch=N           round-queue entries a query wave takes per pull (1..64, default 32)
 //   lstack=N          aux stack words a path-engine query may use (default and maximum PT_LSTACK;
 //                     a query needing more takes the exact DFS)
+//   rays_service=N    ray queries (pt_rayq_create): a wave retires its finished lanes and refills once N
+//                     lanes wait (1..64; 1 = on every trip; default PT_RAYS_SERVICE)
 //   roundlog=1|2|3    per-round kernel times / each round's chains, wall time and rays / and the
 //                     pixels' remaining samples, on stderr
 //   wgprof=FILE       per-workgroup timelines (-DPT_WPROF builds)

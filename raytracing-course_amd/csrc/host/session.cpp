@@ -84,10 +84,8 @@ int flush_trace(pt_session* ss) {
     return trace_wave(ss, spp);
 }
 
-// the scene's copy on the session's device as the kernels see it (without the megakernel's aux BVH)
-pt::SceneView device_view(const pt_session* ss) {
-    const DevScene& ds = *ss->ds;
-    const pt_scene* s = ss->sc;
+// a scene's device copy as the kernels see it (without the megakernel's aux BVH)
+pt::SceneView device_view(const pt_scene* s, const DevScene& ds) {
     pt::SceneView v;
     memset(&v, 0, sizeof(v));
     v.nodes = ds.nodes;
@@ -105,6 +103,7 @@ pt::SceneView device_view(const pt_session* ss) {
     set_blob(v, s, ds.blob);
     return v;
 }
+pt::SceneView device_view(const pt_session* ss) { return device_view(ss->sc, *ss->ds); }
 
 PathShape path_shape(const pt_session* ss, uint32_t chains, bool sparse, bool side) {
     if (chains < ss->lowq && ss->low_grid) return {PT_NQ_BASE, ss->low_grid, pt::path_cmax(PT_NQ_BASE)};

@@ -30,6 +30,9 @@ GATHER_AUTO, GATHER_RCCL, GATHER_HOST = 0, 1, 2
 HANDOFF_SITES = ("suspend", "flush", "ringout", "exact", "side_take", "side_yield", "side_handon", "grow_yield",
                  "grow_handon")
 ABI_VERSION = 6
+# a ray query's hit record (pt_ray_hit, 24 B); a miss is id = -1 with the other fields 0
+HIT_DTYPE = np.dtype([("id", np.int32), ("t", np.float32), ("n", np.float32, (3,)), ("interior", np.uint32)])
+RAYS_CHUNK = 1 << 22   # pt_intersect moves the rays in chunks of at most this many
 
 # One HIP runtime per process: PyTorch bundles its own libamdhip64 (soname
 # libamdhip64.so.7, but its users link the unversioned name), so loading
@@ -110,6 +113,11 @@ _sig = {
     "pt_session_stats": (C.c_int, [_P, C.POINTER(Stats)]),
     "pt_session_stream": (_P, [_P]),
     "pt_session_free": (None, [_P]),
+    "pt_rayq_create": (C.c_int, [_P, C.c_int, C.c_uint64, C.POINTER(_P)]),
+    "pt_rayq_run": (C.c_int, [_P, _P, C.c_uint64, _P, _P]),
+    "pt_rayq_stats": (C.c_int, [_P, C.POINTER(Stats)]),
+    "pt_rayq_free": (None, [_P]),
+    "pt_intersect": (C.c_int, [_P, C.c_int, C.c_uint64, _P, _P, C.POINTER(Stats)]),
     "pt_last_error": (C.c_char_p, []),
     "pt_abi_version": (C.c_int, []),
     "pt_selftest_ray_intersection": (C.c_int, [_P, C.c_int32, C.c_uint32, _P, _P, _P, _P]),
@@ -223,6 +231,17 @@ class Scene:
         _check(_lib.pt_render(self._h, C.byref(o), _ptr(rgb), _ptr(rad), C.byref(st)))
         return rgb, rad, st.as_dict()
 
+    def intersect(self, rays, device=0):
+        """Scene::RayIntersection for the caller's rays on the GPU: `rays` reshapes to (n, 6)
+        float32 (origin, direction; used as given).  Returns (hits, stats): hits is an array of
+        HIT_DTYPE, id = the primitive's index in the prepared order (dump_bvh's; planes at the
+        end), -1 = a miss."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        hits = np.zeros(len(rays), HIT_DTYPE)
+        st = Stats()
+        _check(_lib.pt_intersect(self._h, device, len(rays), _ptr(rays), _ptr(hits), C.byref(st)))
+        return hits, st.as_dict()
+
     # test hooks (host execution of the device traversal code; not a render path)
     def selftest_ray_intersection(self, rays, traversal=TRAVERSAL_REPLAY):
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
@@ -292,6 +311,50 @@ class Session:
             self._h = None
 
     __del__ = close
+
+
+def _addr(x):
+    """a device address: an integer, or any object with data_ptr() (a torch tensor)"""
+    return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else x)
+
+
+class RayQuery:
+    """Closest-hit queries for rays already on the device (include/pt.h ray queries): one
+    context per scene and device, for runs of up to max_rays rays."""
+
+    def __init__(self, scene, device=0, max_rays=RAYS_CHUNK):
+        self.scene = scene
+        self.max_rays = max_rays
+        self._h = _P()
+        _check(_lib.pt_rayq_create(scene._h, device, max_rays, C.byref(self._h)))
+
+    def run(self, rays, hits, n=None, stream=None):
+        """Enqueue n queries on `stream` (a hipStream_t address; None = the null stream).  rays /
+        hits: device addresses, or objects with data_ptr() -- torch tensors of 6 float32 per ray
+        and 24 bytes per hit (HIT_DTYPE), used in place; n defaults to the rays tensor's
+        element count / 6."""
+        if n is None:
+            n = rays.numel() // 6
+        _check(_lib.pt_rayq_run(self._h, stream, n, _addr(rays), _addr(hits)))
+
+    def stats(self):
+        """Wait for the last run; the counters and kernel time of the runs since the last call."""
+        st = Stats()
+        _check(_lib.pt_rayq_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.pt_rayq_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 def tile_owner(t, tiles_x, world):
