@@ -361,6 +361,21 @@ PT_HD bool bvh_prim_intersect(const Prim& P, const Ray& ray, Hit& h) {
     return ok;
 }
 
+// prim_intersect for a box or an ellipsoid (every emitter is one: the light distributions'
+// tests): same operations without the plane and triangle branches and their fields
+PT_HD bool solid_intersect(const Prim& P, const Ray& ray, Hit& h) {
+    const f3 pos = mk3(P.p0.x, P.p0.y, P.p0.z);
+    q4 q; q.x = P.p1.x; q.y = P.p1.y; q.z = P.p1.z; q.w = P.p1.w;
+    const q4 cq = conj(q);
+    Ray lr;
+    lr.o = qrot(cq, ray.o + -1.f * pos);
+    lr.d = qrot(cq, ray.d);
+    const f3 a = mk3(P.p2.x, P.p2.y, P.p2.z);
+    const bool ok = f2u(P.p0.w) == T_BOX ? isect_box(lr, a, h) : isect_ellipsoid(lr, a, h);
+    if (ok) h.n = normalize(qrot(q, h.n));
+    return ok;
+}
+
 // plane-only form of prim_intersect (the scene's plane list): same operations
 PT_HD bool plane_intersect(const Prim& P, const Ray& ray, Hit& h) {
     const f3 pos = mk3(P.p0.x, P.p0.y, P.p0.z);
@@ -375,11 +390,45 @@ PT_HD bool plane_intersect(const Prim& P, const Ray& ray, Hit& h) {
 }
 
 // ------------------------------------------------- light distributions -----
-// src/distributions.cpp:102-110
+// src/distributions.cpp:102-110: three rng_normal calls in a row, with two copies of the polar loop where the three calls
+// inlined would leave three (each run by the lanes whose saved_ok matches).  A lane that enters
+// with a saved value returns it, then draws one pair (a, b, m) and returns b*m and the a*m it
+// has just saved; a lane without one draws a pair, returns b1*m1 and the saved a1*m1, then draws
+// a second pair for b2*m2 and keeps a2*m2.  So every lane draws one pair, and only the lanes
+// that entered without a saved value a second: the same draws and operations per lane, in the
+// same order, as the three calls.
+PT_HD void polar_pair(Rng& r, float& am, float& bm) {
+    float a, b, r2;
+    do {
+        a = (float)((double)(2.0f * rng_uniform(r)) - 1.0);
+        b = (float)((double)(2.0f * rng_uniform(r)) - 1.0);
+        r2 = a * a + b * b;
+    } while (r2 > 1.0f || r2 == 0.0f);
+    const float m = fsqrt(-2.0f * logf_glibc(r2) / r2);
+    am = a * m;
+    bm = b * m;
+}
 PT_HD f3 normal01_vec(Rng& R) {
-    const float f1 = rng_normal(R);
-    const float f2 = rng_normal(R);
-    const float f3_ = rng_normal(R);
+    const bool had = R.saved_ok != 0u;
+    const float s0 = R.saved;
+    float am, bm;
+    polar_pair(R, am, bm);
+    float f1, f2, f3_;
+    if (had) {
+        f1 = s0 * 1.0f + 0.0f;
+        f2 = bm * 1.0f + 0.0f;
+        f3_ = am * 1.0f + 0.0f;
+        R.saved = am;
+        R.saved_ok = 0u;
+    } else {
+        float am2, bm2;
+        polar_pair(R, am2, bm2);
+        f1 = bm * 1.0f + 0.0f;
+        f2 = am * 1.0f + 0.0f;
+        f3_ = bm2 * 1.0f + 0.0f;
+        R.saved = am2;
+        R.saved_ok = 1u;
+    }
     return normalize(mk3(f1, f2, f3_));
 }
 // src/distributions.cpp:144-159
@@ -394,44 +443,44 @@ PT_HD f3 sample_cosine(Rng& R, f3 n) {
 PT_HD float pdf_cosine(f3 n, f3 d) { return smax(0.f, 1.f / PT_PI_F * dot(d, n)); }
 
 // src/distributions.cpp:170-198
-PT_HD int points_for_pdf(const Prim& P, f3 x, f3 d, Hit& h1, Hit& h2) {
-    Ray r; r.o = x; r.d = d;
-    if (!prim_intersect(P, r, h1)) return 0;
+// An emitter's hit along a sampled direction from x: solid_intersect(emitter id, {x, dir}),
+// computed once by sample_mix_e (the light samplers' accept test) and used again by pdf_mix_e
+// as that emitter's first point -- the identical call.  id = ~0u: none.
+struct EmitHit { Hit h; uint32_t id; bool ok; };
+// (ok1, h1 = the first point's solid_intersect(P, {x, d}, h1), done by the caller)
+PT_HD int points_for_pdf(const Prim& P, f3 x, f3 d, bool ok1, const Hit& h1, Hit& h2) {
+    if (!ok1) return 0;
     const float t = h1.t;
     if ((double)t <= 1e-8) return 0;   // reference also prints a stderr diagnostic here
     const float eps = 1e-4f;
     Ray r2; r2.o = x + (t + eps) * d; r2.d = d;
-    if (!prim_intersect(P, r2, h2)) return 1;
+    if (!solid_intersect(P, r2, h2)) return 1;
     h2.t += t + eps;
     return 2;
 }
 
-// src/distributions.cpp:227-269
-PT_HD f3 sample_box(Rng& R, const Prim& B, f3 x) {
+// src/distributions.cpp:227-269: one candidate direction of the rejection loop (the loop
+// and its accept test, the box hit along {x, smp}, are sample_mix_e's)
+PT_HD f3 box_candidate(Rng& R, const Prim& B, f3 x) {
     const f3 s = mk3(B.p2.x, B.p2.y, B.p2.z);
     const float wx = s.x * s.x, wy = s.y * s.y, wz = s.z * s.z;
     const f3 pos = mk3(B.p0.x, B.p0.y, B.p0.z);
     q4 q; q.x = B.p1.x; q.y = B.p1.y; q.z = B.p1.z; q.w = B.p1.w;
-    for (;;) {
-        float u = rng_uniform(R);
-        const float side = (rng_uniform(R) <= 0.5f) ? 1.f : -1.f;
-        u *= wx + wy + wz;
-        float c1 = rng_uniform(R);
-        float c2 = rng_uniform(R);
-        float c3 = rng_uniform(R);
-        c1 = 2.f * c1 - 1.f;
-        c2 = 2.f * c2 - 1.f;
-        c3 = 2.f * c3 - 1.f;
-        f3 pnt = mk3(c1 * s.x, c2 * s.y, c3 * s.z);
-        if (u < wx) pnt.x = side * s.x;
-        else if (u < wx + wy) pnt.y = side * s.y;
-        else pnt.z = side * s.z;
-        const f3 on_box = qrot(q, pnt) + pos;
-        const f3 smp = normalize(on_box - x);
-        Hit h;
-        Ray r; r.o = x; r.d = smp;
-        if (prim_intersect(B, r, h)) return smp;
-    }
+    float u = rng_uniform(R);
+    const float side = (rng_uniform(R) <= 0.5f) ? 1.f : -1.f;
+    u *= wx + wy + wz;
+    float c1 = rng_uniform(R);
+    float c2 = rng_uniform(R);
+    float c3 = rng_uniform(R);
+    c1 = 2.f * c1 - 1.f;
+    c2 = 2.f * c2 - 1.f;
+    c3 = 2.f * c3 - 1.f;
+    f3 pnt = mk3(c1 * s.x, c2 * s.y, c3 * s.z);
+    if (u < wx) pnt.x = side * s.x;
+    else if (u < wx + wy) pnt.y = side * s.y;
+    else pnt.z = side * s.z;
+    const f3 on_box = qrot(q, pnt) + pos;
+    return normalize(on_box - x);
 }
 // src/distributions.cpp:271-287 (1./(8W) and the final quotient are f64 ops
 // rounded to float: identical to the f32 ops, double rounding is innocuous)
@@ -441,9 +490,9 @@ PT_HD float pdf_point_box(const Prim& B, float dist2, f3 n, f3 d) {
     return (p_y * dist2) / fabs_(dot(d, n));
 }
 // src/distributions.cpp:289-312
-PT_HD float pdf_box(const Prim& B, f3 x, f3 d) {
-    Hit h1, h2;
-    const int k = points_for_pdf(B, x, d, h1, h2);
+PT_HD float pdf_box(const Prim& B, f3 x, f3 d, bool ok1, const Hit& h1) {
+    Hit h2;
+    const int k = points_for_pdf(B, x, d, ok1, h1, h2);
     if (k == 0) return 1e-9f;
     const f3 cp = x + h1.t * d;
     float sum = pdf_point_box(B, dot(x - cp, x - cp), h1.n, d);
@@ -453,19 +502,14 @@ PT_HD float pdf_box(const Prim& B, f3 x, f3 d) {
     }
     return sum;
 }
-// src/distributions.cpp:318-338
-PT_HD f3 sample_ellipsoid(Rng& R, const Prim& E, f3 x) {
+// src/distributions.cpp:318-338: one candidate direction (as box_candidate)
+PT_HD f3 ellipsoid_candidate(Rng& R, const Prim& E, f3 x) {
     const f3 rr = mk3(E.p2.x, E.p2.y, E.p2.z);
     const f3 pos = mk3(E.p0.x, E.p0.y, E.p0.z);
     q4 q; q.x = E.p1.x; q.y = E.p1.y; q.z = E.p1.z; q.w = E.p1.w;
-    for (;;) {
-        const f3 k = normal01_vec(R);
-        const f3 on = qrot(q, rr * k) + pos;
-        const f3 smp = normalize(on - x);
-        Hit h;
-        Ray r; r.o = x; r.d = smp;
-        if (prim_intersect(E, r, h)) return smp;
-    }
+    const f3 k = normal01_vec(R);
+    const f3 on = qrot(q, rr * k) + pos;
+    return normalize(on - x);
 }
 // src/distributions.cpp:340-347
 PT_HD float pdf_point_ellipsoid(const Prim& E, float dist2, f3 y, f3 n_, f3 d) {
@@ -477,9 +521,9 @@ PT_HD float pdf_point_ellipsoid(const Prim& E, float dist2, f3 y, f3 n_, f3 d) {
     return (p_y * dist2) / fabs_(dot(d, n_));
 }
 // src/distributions.cpp:349-372
-PT_HD float pdf_ellipsoid(const Prim& E, f3 x, f3 d) {
-    Hit h1, h2;
-    const int k = points_for_pdf(E, x, d, h1, h2);
+PT_HD float pdf_ellipsoid(const Prim& E, f3 x, f3 d, bool ok1, const Hit& h1) {
+    Hit h2;
+    const int k = points_for_pdf(E, x, d, ok1, h1, h2);
     if (k == 0) return 1e-9f;
     const f3 cp = x + h1.t * d;
     float sum = pdf_point_ellipsoid(E, dot(x - cp, x - cp), cp, h1.n, d);
@@ -495,33 +539,65 @@ struct EmitGlobal {
     const SceneView& S;
     PT_HD Prim operator()(uint32_t k) const { return S.prims[S.emitters[k]]; }
 };
-// src/distributions.cpp:385-399
+// src/distributions.cpp:385-399.  The light samplers' rejection loops (:227-269, :318-338) are
+// one loop here: light lanes draw a candidate, every pending lane intersects its emitter along
+// its direction, light lanes accept on a hit.  A cosine lane goes through once with emitter 0
+// and its own direction: pdf_mix_e's first call for that emitter, made here where the wave is
+// converged.  `eh` returns the hit (id = ~0u without emitters).  A lane's draws keep their order.
 template <class EM>
-PT_HD f3 sample_mix_e(const SceneView& S, const EM& em, Rng& R, f3 x, f3 n) {
+PT_HD f3 sample_mix_e(const SceneView& S, const EM& em, Rng& R, f3 x, f3 n, EmitHit& eh) {
     const float flip = rng_uniform(R);
-    if (S.n_emitters == 0u || flip <= 0.5f) return sample_cosine(R, n);
-    const float fid = rng_uniform(R);
-    const uint32_t id = (uint32_t)floorf(fid * (float)S.n_emitters);
+    eh.h.t = 0.f; eh.h.n = mk3(0.f, 0.f, 0.f); eh.h.interior = 0u;
+    eh.id = 0xffffffffu;
+    eh.ok = false;
+    if (S.n_emitters == 0u) return sample_cosine(R, n);
+    const bool light = !(flip <= 0.5f);
+    f3 dir = n;
+    uint32_t id = 0u;
+    if (light) {
+        const float fid = rng_uniform(R);
+        id = (uint32_t)floorf(fid * (float)S.n_emitters);
+    } else {
+        dir = sample_cosine(R, n);
+    }
     const Prim E = em(id);
-    return f2u(E.p0.w) == T_BOX ? sample_box(R, E, x) : sample_ellipsoid(R, E, x);
+    const bool box = f2u(E.p0.w) == T_BOX;
+    for (;;) {
+        if (light) dir = box ? box_candidate(R, E, x) : ellipsoid_candidate(R, E, x);
+        Ray r; r.o = x; r.d = dir;
+        eh.ok = solid_intersect(E, r, eh.h);
+        if (eh.ok || !light) break;
+    }
+    eh.id = id;
+    return dir;
 }
-PT_HD f3 sample_mix(const SceneView& S, Rng& R, f3 x, f3 n) { return sample_mix_e(S, EmitGlobal{S}, R, x, n); }
-// src/distributions.cpp:401-416
+PT_HD f3 sample_mix(const SceneView& S, Rng& R, f3 x, f3 n, EmitHit& eh) {
+    return sample_mix_e(S, EmitGlobal{S}, R, x, n, eh);
+}
+// src/distributions.cpp:401-416; `eh` = sample_mix_e's hit for (x, d)
 template <class EM>
-PT_HD float pdf_mix_e(const SceneView& S, const EM& em, f3 x, f3 n, f3 d) {
+PT_HD float pdf_mix_e(const SceneView& S, const EM& em, f3 x, f3 n, f3 d, const EmitHit& eh) {
     float sum = pdf_cosine(n, d);
     if (S.n_emitters != 0u) {
         float ps = 0.f;
         for (uint32_t k = 0; k < S.n_emitters; ++k) {
             const Prim E = em(k);
-            ps += f2u(E.p0.w) == T_BOX ? pdf_box(E, x, d) : pdf_ellipsoid(E, x, d);
+            Hit h1 = eh.h;
+            bool ok1 = eh.ok;
+            if (k != eh.id) {
+                Ray r; r.o = x; r.d = d;
+                ok1 = solid_intersect(E, r, h1);
+            }
+            ps += f2u(E.p0.w) == T_BOX ? pdf_box(E, x, d, ok1, h1) : pdf_ellipsoid(E, x, d, ok1, h1);
         }
         ps *= S.inv_emitters;   // = 1.f / (float)S.n_emitters (IEEE division on the host)
         sum = 0.5f * sum + 0.5f * ps;
     }
     return sum;
 }
-PT_HD float pdf_mix(const SceneView& S, f3 x, f3 n, f3 d) { return pdf_mix_e(S, EmitGlobal{S}, x, n, d); }
+PT_HD float pdf_mix(const SceneView& S, f3 x, f3 n, f3 d, const EmitHit& eh) {
+    return pdf_mix_e(S, EmitGlobal{S}, x, n, d, eh);
+}
 
 // src/scene.cpp:79-81
 PT_HD f3 reflect(f3 n, f3 dir) { return dir - (2.0f * n) * dot(n, dir); }

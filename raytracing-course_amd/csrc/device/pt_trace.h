@@ -507,10 +507,11 @@ PT_HD bool shade_vertex_e(const SceneView& S, const EM& em, const Shade& sh, Rng
     const f3 n = h.n;
     if (mat == M_DIFFUSE) {
         const f3 p_outer = p + eps * n;
-        const f3 dir = sample_mix_e(S, em, R, p_outer, n);
+        EmitHit eh;
+        const f3 dir = sample_mix_e(S, em, R, p_outer, n, eh);
         const float cosv = dot(dir, n);
         if (cosv <= 0.f) { idm = (uint32_t)id | (V_TERM << 30); s1 = s2 = 0.f; return false; }
-        const float pw = pdf_mix_e(S, em, p_outer, n, dir);
+        const float pw = pdf_mix_e(S, em, p_outer, n, dir, eh);
         idm = (uint32_t)id | (V_DIFFUSE << 30);
         s1 = cosv;
         s2 = 1.f / pw;

@@ -193,7 +193,8 @@ __global__ void __launch_bounds__(64) k_wexact(WaveParams P) {
     wave_add_u64(ctr + 4, err);
 }
 
-__global__ void __launch_bounds__(256) k_wshade(WaveParams P) {
+// (5 waves per SIMD asked for: the allocator otherwise ends one register over the 96 they allow)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) k_wshade(WaveParams P) {
     __shared__ uint32_t agg[5];
     uint32_t* out = P.ctl + PT_CTL_SET * (1u - P.parity);
     // the exact-DFS results of this round (the path engine shades everything else itself)
