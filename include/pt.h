@@ -276,6 +276,13 @@ int pt_selftest_render_host(pt_scene* s, int32_t traversal, uint32_t x0, uint32_
                             uint32_t spp, float* radiance);
 /* the 256-entry gamma threshold table used by the device tonemap */
 int pt_selftest_gamma_table(const pt_scene* s, float* thr256);
+/* session set-up without a device: the geometry (o's rank, world, window, traversal; o->device is
+ * ignored), the wavefront pass's launch shapes and capacities on a device of `cus` compute units,
+ * and the arena's layout, as "key=value" lines in buf (cap bytes; PT_E_INVALID if too small): a
+ * line per plan field (mix and mix_low: four values), then n_slots, n_tiles_local, arena_bytes and
+ * aux_stack_words (the scene's wide aux traversal stack, which a carry record holds).
+ * Prepares the scene if needed. */
+int pt_selftest_wave_plan(pt_scene* s, const pt_session_opts* o, uint32_t cus, char* buf, size_t cap);
 
 #ifdef __cplusplus
 }

@@ -60,7 +60,7 @@ struct TraceParams {
     CamView cam;
     TileMap tm;
     PixelState st;
-    unsigned long long* counters; // rays, nodes, prim tests, plane tests, errors, aux visits, fallbacks
+    unsigned long long* counters; // statistics counters (the CTR_* slots below)
     ReplayCfg cfg;
     uint32_t depth;
     uint32_t spp;
@@ -113,7 +113,7 @@ struct WaveParams {
     uint2* endq;                  // per path workgroup path_cmax(NQ) entries: its shade wave's ended paths
                                   // {slot | miss << 31, LDS pixel-table entry}
     uint32_t* ctl;                // 2 x PT_CTL_SET round counters
-    unsigned long long* counters; // rays, nodes, prim tests, plane tests, errors, aux visits, fallbacks, ray fallbacks
+    unsigned long long* counters; // statistics counters (the CTR_* slots below)
     uint32_t depth;
     uint32_t parity;
     uint32_t target;              // samples per pixel to reach in this pass
@@ -331,10 +331,21 @@ struct ResolveParams {
     unsigned long long* counters; // statistics counters: C_SHORT counts the owned pixels whose
                                   // samples done differ from `samples` (a lost chain; must be 0)
 };
-// statistics counter slots (per copy, PT_CTR_STRIDE u64) besides rays .. fallbacks_ray (0-7)
-// and the cooperative engine's share (8-10, 13); CTR_HO + PT_HO_*: the items handed on at
-// each hand-off site (include/pt.h PT_HO_*; DESIGN.md §4 "Hand-off sites")
-enum : uint32_t { CTR_SHORT = 11u, CTR_HANDON = 12u, CTR_HO = 16u };
+// statistics counter slots (per copy, PT_CTR_STRIDE u64): pt_stats' rays .. fallbacks_ray, the
+// cooperative engine's share of them (CTR_COOP_*), the resolve's short pixels, the chains handed
+// on; CTR_HO + PT_HO_*: the items handed on at each hand-off site (include/pt.h PT_HO_*;
+// DESIGN.md §4 "Hand-off sites")
+enum : uint32_t {
+    CTR_RAYS = 0u, CTR_NODES = 1u, CTR_PTESTS = 2u, CTR_PLANES = 3u, CTR_ERRORS = 4u, CTR_AUX = 5u,
+    CTR_FALLBACKS = 6u, CTR_FALLBACKS_RAY = 7u, CTR_COOP_RAYS = 8u, CTR_COOP_NODES = 9u, CTR_COOP_PTESTS = 10u,
+    CTR_SHORT = 11u, CTR_HANDON = 12u, CTR_COOP_AUX = 13u, CTR_HO = 16u
+};
+// (the 14 named slots are distinct -- together exactly bits 0-13 -- and lie below CTR_HO)
+static_assert((1u << CTR_RAYS | 1u << CTR_NODES | 1u << CTR_PTESTS | 1u << CTR_PLANES | 1u << CTR_ERRORS |
+               1u << CTR_AUX | 1u << CTR_FALLBACKS | 1u << CTR_FALLBACKS_RAY | 1u << CTR_COOP_RAYS |
+               1u << CTR_COOP_NODES | 1u << CTR_COOP_PTESTS | 1u << CTR_SHORT | 1u << CTR_HANDON |
+               1u << CTR_COOP_AUX) == (1u << 14) - 1u && 14u <= CTR_HO,
+              "statistics counter slots: two names share a slot, or one reaches the hand-off sites");
 // the hand-off sites (include/pt.h PT_HO_*, which the host checks these against)
 enum : uint32_t { HO_SUSPEND = 0u, HO_FLUSH, HO_RINGOUT, HO_EXACT, HO_SIDE_TAKE, HO_SIDE_YIELD, HO_SIDE_HANDON,
                   HO_GROW_YIELD, HO_GROW_HANDON, HO_N };

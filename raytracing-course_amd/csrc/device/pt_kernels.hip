@@ -70,13 +70,13 @@ __global__ void __launch_bounds__(256) k_trace(TraceParams P) {
         store_sum(P.st, slot, sum, y * P.tm.W + x);
     }
     unsigned long long* ctr = ctr_copy(P.counters);
-    wave_add_u64(ctr + 0, C.rays);
-    wave_add_u64(ctr + 1, C.nodes);
-    wave_add_u64(ctr + 2, C.ptests);
-    wave_add_u64(ctr + 3, C.planes);
-    wave_add_u64(ctr + 4, (unsigned long long)C.errs);
-    wave_add_u64(ctr + 5, C.aux);
-    wave_add_u64(ctr + 6, C.fallbacks);
+    wave_add_u64(ctr + CTR_RAYS, C.rays);
+    wave_add_u64(ctr + CTR_NODES, C.nodes);
+    wave_add_u64(ctr + CTR_PTESTS, C.ptests);
+    wave_add_u64(ctr + CTR_PLANES, C.planes);
+    wave_add_u64(ctr + CTR_ERRORS, (unsigned long long)C.errs);
+    wave_add_u64(ctr + CTR_AUX, C.aux);
+    wave_add_u64(ctr + CTR_FALLBACKS, C.fallbacks);
     if (P.wg_prof) {
         __syncthreads();
         if (threadIdx.x == 0) {

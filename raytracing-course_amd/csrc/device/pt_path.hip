@@ -418,15 +418,15 @@ __device__ __forceinline__ void path_retire(PathLds<NQ>& L, uint32_t wq, bool& a
 // the wave's counters to this XCD's statistics copy
 __device__ __forceinline__ void path_flush_counts(const WaveParams& P, const PathCounts& N) {
     unsigned long long* ctr = ctr_copy(P.counters);
-    wave_add_u64(ctr + 1, N.C.nodes);
-    wave_add_u64(ctr + 2, N.C.ptests);
-    wave_add_u64(ctr + 5, N.C.aux);
+    wave_add_u64(ctr + CTR_NODES, N.C.nodes);
+    wave_add_u64(ctr + CTR_PTESTS, N.C.ptests);
+    wave_add_u64(ctr + CTR_AUX, N.C.aux);
     if (lane_id() == 0u) {
-        if (N.rays) atomicAdd(ctr + 0, (unsigned long long)N.rays);
-        if (N.rays && P.S.n_planes) atomicAdd(ctr + 3, (unsigned long long)N.rays * P.S.n_planes);
-        if (N.fallbacks) atomicAdd(ctr + 6, (unsigned long long)N.fallbacks);
+        if (N.rays) atomicAdd(ctr + CTR_RAYS, (unsigned long long)N.rays);
+        if (N.rays && P.S.n_planes) atomicAdd(ctr + CTR_PLANES, (unsigned long long)N.rays * P.S.n_planes);
+        if (N.fallbacks) atomicAdd(ctr + CTR_FALLBACKS, (unsigned long long)N.fallbacks);
         if (N.fallbacks) atomicAdd(ctr + CTR_HO + HO_EXACT, (unsigned long long)N.fallbacks);
-        if (N.init_exact) atomicAdd(ctr + 7, (unsigned long long)N.init_exact);
+        if (N.init_exact) atomicAdd(ctr + CTR_FALLBACKS_RAY, (unsigned long long)N.init_exact);
     }
 }
 

@@ -27,8 +27,8 @@ struct RaysParams {
     unsigned long long* head;
     uint32_t* exact_n;
     uint32_t* exact;              // the exact list: indices of the rays the replay hands to the exact DFS
-    unsigned long long* counters; // PT_CTR_COPIES x PT_CTR_STRIDE: rays, nodes, prim tests, plane tests, errors,
-                                  // aux visits, fallbacks, ray fallbacks (0-7 of each copy)
+    unsigned long long* counters; // PT_CTR_COPIES x PT_CTR_STRIDE statistics counters (pt_kernels.h CTR_RAYS ..
+                                  // CTR_FALLBACKS_RAY of each copy)
     uint32_t aux_words;           // k_rays: aux stack words per lane (LDS; + a trash word)
     uint32_t dfs_words;           // k_rays_exact: exact DFS stack words per lane (LDS; + a trash word)
 };

@@ -40,14 +40,14 @@ struct RayStats {
     uint32_t rays = 0u, err = 0u, exact = 0u, exact_ray = 0u;
     __device__ __forceinline__ void flush(unsigned long long* counters) const {
         unsigned long long* ctr = ctr_copy(counters);
-        wave_add_u64(ctr + 0, rays);
-        wave_add_u64(ctr + 1, C.nodes);
-        wave_add_u64(ctr + 2, C.ptests);
-        wave_add_u64(ctr + 3, C.planes);
-        wave_add_u64(ctr + 4, err);
-        wave_add_u64(ctr + 5, C.aux);
-        wave_add_u64(ctr + 6, exact);
-        wave_add_u64(ctr + 7, exact_ray);
+        wave_add_u64(ctr + CTR_RAYS, rays);
+        wave_add_u64(ctr + CTR_NODES, C.nodes);
+        wave_add_u64(ctr + CTR_PTESTS, C.ptests);
+        wave_add_u64(ctr + CTR_PLANES, C.planes);
+        wave_add_u64(ctr + CTR_ERRORS, err);
+        wave_add_u64(ctr + CTR_AUX, C.aux);
+        wave_add_u64(ctr + CTR_FALLBACKS, exact);
+        wave_add_u64(ctr + CTR_FALLBACKS_RAY, exact_ray);
     }
 };
 

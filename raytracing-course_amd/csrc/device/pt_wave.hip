@@ -188,9 +188,9 @@ __global__ void __launch_bounds__(64) k_wexact(WaveParams P) {
         P.done.id[j] = id < 0 ? 0xffffffffu : (uint32_t)id;
     }
     unsigned long long* ctr = ctr_copy(P.counters);
-    wave_add_u64(ctr + 1, C.nodes);
-    wave_add_u64(ctr + 2, C.ptests);
-    wave_add_u64(ctr + 4, err);
+    wave_add_u64(ctr + CTR_NODES, C.nodes);
+    wave_add_u64(ctr + CTR_PTESTS, C.ptests);
+    wave_add_u64(ctr + CTR_ERRORS, err);
 }
 
 // (5 waves per SIMD asked for: the allocator otherwise ends one register over the 96 they allow)

@@ -625,8 +625,10 @@ __device__ __forceinline__ void lc_flush(uint32_t* lc) {
     const WaveParams& K = karg<WaveParams>();
     unsigned long long* ctr = ctr_copy(K.counters);
     const bool grow = (K.side_flags & PT_STOP_GROW) != 0u;
-    const uint32_t total[LC_HANDED + 1u] = {0u, 1u, 2u, CTR_HO + (grow ? HO_GROW_YIELD : HO_SIDE_YIELD), 5u, 6u, CTR_HANDON};
-    const uint32_t share[LC_HANDED + 1u] = {8u, 9u, 10u, 0u, 13u, 0u, CTR_HO + (grow ? HO_GROW_HANDON : HO_SIDE_HANDON)};
+    const uint32_t total[LC_HANDED + 1u] = {CTR_RAYS, CTR_NODES, CTR_PTESTS, CTR_HO + (grow ? HO_GROW_YIELD : HO_SIDE_YIELD),
+                                             CTR_AUX, CTR_FALLBACKS, CTR_HANDON};
+    const uint32_t share[LC_HANDED + 1u] = {CTR_COOP_RAYS, CTR_COOP_NODES, CTR_COOP_PTESTS, 0u, CTR_COOP_AUX, 0u,
+                                             CTR_HO + (grow ? HO_GROW_HANDON : HO_SIDE_HANDON)};
 #pragma unroll
     for (uint32_t k = 0; k <= LC_HANDED; ++k) {
         const uint32_t v = lc[k];
@@ -634,7 +636,7 @@ __device__ __forceinline__ void lc_flush(uint32_t* lc) {
         atomicAdd(ctr + total[k], (unsigned long long)v);
         if (share[k]) atomicAdd(ctr + share[k], (unsigned long long)v);
         // (every counted ray tests every plane)
-        if (k == LC_RAYS && K.S.n_planes) atomicAdd(ctr + 3, (unsigned long long)v * K.S.n_planes);
+        if (k == LC_RAYS && K.S.n_planes) atomicAdd(ctr + CTR_PLANES, (unsigned long long)v * K.S.n_planes);
         lc[k] = 0u;
     }
 }

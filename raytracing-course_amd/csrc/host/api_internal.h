@@ -5,11 +5,13 @@
 //                 the scene's device copy, pt_device_init
 //   scene_api.cpp Scene::Load / InitScene equivalents: parse, reference BVH, aux BVH,
 //                 the query blob (pt_scene_*)
-//   session.cpp   tile sessions: set-up, the megakernel pass, resolve, stats (pt_session_*)
+//   session.cpp   tile sessions: set-up (geometry, arena), the megakernel pass, resolve, stats (pt_session_*)
+//   wave_plan.cpp the wavefront pass's launch shapes and capacities (plan_wave: no device needed)
 //   rounds.cpp    the wavefront pass: path rounds, early / final cooperative launches
 //   render.cpp    Scene::Render equivalent: per-GPU threads, the RCCL / host gather, PPM
 //   rayq.cpp      the ray-query engine: closest-hit queries for the caller's rays (pt_rayq_*, pt_intersect)
-//   selftest.cpp  host execution of the device query / integrator code (tests only)
+//   selftest.cpp  host execution of the device query / integrator code (tests only; the fourth
+//                 hook, pt_selftest_wave_plan, is in session.cpp beside the set-up it reports)
 #pragma once
 #include "pt.h"
 
@@ -143,15 +145,62 @@ pt::SceneView device_view(const pt_scene* s, const DevScene& ds);   // ... of an
 // the hand-off site named `name` (PT_HO_*: "suspend", "flush", "ringout", "exact", "side_take",
 // "side_yield", "side_handon", "grow_yield", "grow_handon"), or -1
 int handoff_site(const char* name);
-// a scene beyond the cooperative engine's LDS tables (RAY_DEPTH > QC_FOLD, more than
-// QC_NPL planes or QC_NEM emitters) runs its BIG instantiation
-bool coop_big(const pt_session* ss);
+// the summed counter block's slots CTR_RAYS .. CTR_FALLBACKS_RAY as pt_stats' rays .. fallbacks_ray
+void counter_stats(const unsigned long long* c, pt_stats* st);
+
+// The wavefront pass's launch shapes and capacities (wave_plan.cpp): fixed at session creation,
+// a function of the scene's tree facts, the CU count, the owned pixels and PT_TUNE.  (Run state
+// and device pointers are pt_session's.)
+struct WavePlan {
+    uint32_t shade_grid = 0;      // (read by no launch: path rounds run k_wshade on 64 workgroups)
+    uint32_t path_budget = 1024, path_ticks = 0, low_ticks = 0;
+    // the full rounds' shape: query waves per workgroup (PT_TUNE nq: 2 or 3) and its grid; path_grid is
+    // the grid of the NQ = 2 launches (low-chain rounds at most low_grid of it, the sparse kernel)
+    uint32_t full_nq = PT_NQ_FULL, path_grid = 0, full_grid = 0;
+    uint32_t carry_words = 0;     // words of a suspended query's record
+    uint32_t lane_cap = 0;        // min(pixels, query lanes): what one round can suspend
+    uint32_t carry_cap = 0;       // ... and what the early launch yields besides: the carry queue's entries
+    bool runend_auto = false;     // path_runend follows the launch's shape (a few chains per query wave)
+    uint32_t path_runend = 0, path_sparse = 0, sparse_steps = 8;
+    uint32_t coop_max = 0, coop_grid = 0, coop_reserve = 0;   // cooperative engine (k_wcoop) at the end of a pass
+    uint32_t coop_team = 4;       // lanes per chain in the cooperative engine (pure-coop rate, teams of
+                                  // 64 / 32 / 16 / 8: 283 / 392 / 572 / 815 Mray/s; the final launch in
+                                  // teams of 4 against 8, rank 0 of 1 / 8: 475.9 / 74.7 ms against
+                                  // 476.3 / 79.2, means of 5 interleaved runs, profiles/r06_coop/team4)
+    bool coop_order = true;       // the cooperative engine takes the pixels furthest from the target first
+    uint32_t coop_grow = 0;       // the final launch's last chains handed to whole-wave teams (0: never)
+    uint32_t coop_grow_mid = 0;   // ... and an earlier stage of teams of 32 (0: none)
+    uint32_t round_batch = 1;     // rounds launched per count while the chains are far above the hand-over
+    // early cooperative launch: once a pass's chains fall below early_at, the early_k chains
+    // with the most samples left run in a cooperative launch on a second stream (early_wg
+    // workgroups per CU, beside the path engine's low-chain rounds) to the end of the pass
+    uint32_t early_wg = 1, early_at = 0, early_k = 0, side_team = 8;
+    // k_wpath's per-trip step mix: {probe_every, probe_min, aux_extra, end_min}, and the one of
+    // rounds that start with fewer than lowq chains (latency-bound: few chains per lane)
+    uint32_t mix[4] = {PT_PROBE_EVERY, PT_PROBE_MIN, PT_AUX2, PT_END_MIN},
+             mix_low[4] = {PT_PROBE_EVERY, PT_PROBE_MIN, PT_AUX2, PT_END_MIN_LOW};
+    uint32_t lowq = 0;
+    uint32_t low_grid = 0;        // path workgroups of those rounds
+    // a scene beyond the cooperative engine's LDS tables (RAY_DEPTH > QC_FOLD, more than
+    // QC_NPL planes or QC_NEM emitters) runs its BIG instantiation
+    bool big = false;
+};
+struct PlanInputs {
+    uint32_t cus = 0;                                     // the device's compute units
+    uint32_t n_slots = 0, n_tiles_local = 0, depth = 0;   // the session's pixels and RAY_DEPTH
+    uint32_t n_planes = 0, n_emitters = 0;
+    uint32_t auxw_stack = 0, auxsl_depth = 0, max_stack = 0, n_aux = 0;   // the scene's tree facts (pt_scene)
+};
+// PT_OK, or PT_E_INVALID for a PT_TUNE value no plan has (nq)
+int plan_wave(const PlanInputs& in, WavePlan* out);
+// the plan as "key=value" lines, a line per field (pt_selftest_wave_plan)
+std::string plan_text(const WavePlan& w);
 // a path round's launch shape: query waves per workgroup, workgroups, and the chains a
 // workgroup holds at most.  Full rounds (at least lowq chains, not the sparse kernel) run the
-// session's full shape; low-chain rounds, the sparse kernel and a round beside the early
+// plan's full shape; low-chain rounds, the sparse kernel and a round beside the early
 // cooperative launch (`side`: its workgroup's LDS must fit beside the round's) NQ = 2.
 struct PathShape { uint32_t nq, grid, cmax; };
-PathShape path_shape(const pt_session* ss, uint32_t chains, bool sparse, bool side);
+PathShape path_shape(const WavePlan& w, uint32_t chains, bool sparse, bool side);
 
 static_assert(pt::HO_SUSPEND == PT_HO_SUSPEND && pt::HO_FLUSH == PT_HO_FLUSH && pt::HO_RINGOUT == PT_HO_RINGOUT &&
                   pt::HO_EXACT == PT_HO_EXACT && pt::HO_SIDE_TAKE == PT_HO_SIDE_TAKE &&
@@ -210,27 +259,11 @@ struct pt_session {
     uint8_t* fb = nullptr;            // rank 0: the window's row-major framebuffer (device)
     float* rad = nullptr;
     unsigned long long* wg_prof = nullptr;
-    // wavefront engine buffers (replay traversal)
+    // wavefront engine (replay traversal): its plan, fixed at creation, and its buffers
     bool wave = false;
-    uint32_t path_grid = 0, path_budget = 1024, path_ticks = 0, low_ticks = 0, path_runend = 0, path_sparse = 0, sparse_steps = 8;
-    // the full rounds' shape: query waves per workgroup (PT_TUNE nq: 2 or 3) and its grid; path_grid is
-    // the grid of the NQ = 2 launches (low-chain rounds at most low_grid of it, the sparse kernel)
-    uint32_t full_nq = PT_NQ_FULL, full_grid = 0;
-    bool runend_auto = false;     // path_runend follows the launch's shape (a few chains per query wave)
-    uint32_t coop_max = 0, coop_grid = 0, coop_reserve = 0;   // cooperative engine (k_wcoop) at the end of a pass
-    uint32_t round_batch = 1;     // rounds launched per count while the chains are far above the hand-over
-    // k_wpath's per-trip step mix: {probe_every, probe_min, aux_extra, end_min}, and the one of
-    // rounds that start with fewer than lowq chains (latency-bound: few chains per lane)
-    uint32_t mix[4] = {PT_PROBE_EVERY, PT_PROBE_MIN, PT_AUX2, PT_END_MIN},
-             mix_low[4] = {PT_PROBE_EVERY, PT_PROBE_MIN, PT_AUX2, PT_END_MIN_LOW};
-    uint32_t lowq = 0;
-    uint32_t low_grid = 0;        // path workgroups of those rounds
-    bool coop_order = true;       // the cooperative engine takes the pixels furthest from the target first
+    pti::WavePlan plan;
     uint32_t* order = nullptr;    // 2 x 256 bucket counters + the intake order (a round's work: <= pixels)
-    // early cooperative launch: once a pass's chains fall below early_at, the early_k chains
-    // with the most samples left run in a cooperative launch on a second stream (early_wg
-    // workgroups per CU, beside the path engine's low-chain rounds) to the end of the pass
-    uint32_t early_k = 0, early_at = 0, early_wg = 1, side_team = 8;
+    // the early cooperative launch (plan.early_k chains on a second stream)
     pt::RayQ side = {};           // its queue (early_k entries) ...
     uint32_t* side_carry = nullptr;   // ... its suspended queries' restart records (early_k x carry_words)
     uint32_t* side_ctl = nullptr;     // ... and its two round-counter sets
@@ -238,28 +271,20 @@ struct pt_session {
     hipEvent_t side_taken = nullptr, side_end = nullptr;   // its queue is taken / it has stopped
     std::thread side_th;          // makes the three above (joined before their first use)
     hipError_t side_rc = hipSuccess;
-    uint32_t coop_grow = 0;       // the final launch's last chains handed to whole-wave teams (0: never)
-    uint32_t coop_grow_mid = 0;   // ... and an earlier stage of teams of 32 (0: none)
-    uint32_t coop_team = 4;       // lanes per chain in the cooperative engine (pure-coop rate, teams of
-                                  // 64 / 32 / 16 / 8: 283 / 392 / 572 / 815 Mray/s; the final launch in
-                                  // teams of 4 against 8, rank 0 of 1 / 8: 475.9 / 74.7 ms against
-                                  // 476.3 / 79.2, means of 5 interleaved runs, profiles/r06_coop/team4)
     // every device buffer below lives in one allocation (pt_session_create)
     unsigned char* arena = nullptr;
     size_t arena_bytes = 0;
     pt::RayQ fq[2] = {};          // fresh rays (n_slots each)
     pt::DoneQ done = {};          // exact-DFS results (n_slots)
     pt::RayQ ex = {};             // rays handed to the exact DFS (n_slots)
-    uint32_t* carry = nullptr;    // 2 * carry_cap * carry_words
+    uint32_t* carry = nullptr;    // 2 * plan.carry_cap * plan.carry_words
     uint2* endq = nullptr;        // grid * path_cmax(nq) of the larger shape: the shade waves' ended paths
     unsigned long long short_seen = 0;   // CTR_SHORT at the last resolve
-    uint32_t lane_cap = 0;        // min(pixels, query lanes): what one round can suspend
-    uint32_t carry_cap = 0, carry_words = 0;
     uint32_t* ctl = nullptr;      // 2 x PT_CTL_SET round counters
     uint32_t* ctl_host = nullptr; // pinned copy of one counter set
     double roundlog_t = 0.0;      // (roundlog>=2: the last round's end, host clock, and the rays by then)
     unsigned long long roundlog_rays = 0;
-    uint32_t shade_grid = 0, rounds = 0;
+    uint32_t rounds = 0;
     hipStream_t stream = nullptr;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;   // the passes' event pairs (kernel_ms)
     struct LaunchEvents {

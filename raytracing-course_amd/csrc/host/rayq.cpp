@@ -115,14 +115,7 @@ int pt_rayq_stats(pt_rayq* q, pt_stats* st) {
         q->seen[k] = sum;
     }
     memset(st, 0, sizeof(*st));
-    st->rays = c[0];
-    st->node_visits = c[1];
-    st->prim_tests = c[2];
-    st->plane_tests = c[3];
-    st->errors = c[4];
-    st->aux_visits = c[5];
-    st->fallbacks = c[6];
-    st->fallbacks_ray = c[7];
+    counter_stats(c, st);
     st->kernel_ms = q->kernel_ms;
     q->kernel_ms = 0.0;
     // algorithmic bytes per counted unit, as a wavefront session reports them

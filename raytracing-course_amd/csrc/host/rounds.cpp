@@ -46,9 +46,9 @@ int fill_params(pt_session* ss, uint32_t spp, const PassTune& t, pt::WaveParams&
     wp.ex = ss->ex;
     wp.endq = ss->endq;
     wp.cq[0] = ss->carry;
-    wp.cq[1] = ss->carry + (size_t)ss->carry_cap * ss->carry_words;
-    wp.carry_cap = ss->carry_cap;
-    wp.carry_words = ss->carry_words;
+    wp.cq[1] = ss->carry + (size_t)ss->plan.carry_cap * ss->plan.carry_words;
+    wp.carry_cap = ss->plan.carry_cap;
+    wp.carry_words = ss->plan.carry_words;
     wp.ctl = ss->ctl;
     wp.counters = ss->counters;
     wp.depth = ss->depth;
@@ -57,17 +57,17 @@ int fill_params(pt_session* ss, uint32_t spp, const PassTune& t, pt::WaveParams&
     wp.max_stack = std::max<uint32_t>(s->max_stack, 1u);
     wp.aux_stack = std::max<uint32_t>(s->auxw_stack, 1u);
     wp.path = 1u;
-    wp.path_budget = ss->path_budget;
-    wp.path_ticks = ss->path_ticks;
+    wp.path_budget = ss->plan.path_budget;
+    wp.path_ticks = ss->plan.path_ticks;
     // (path_runend and path_cap: per round, from its launch's shape -- path_round)
     wp.tile_order = ss->tile_order;
-    wp.sparse_steps = ss->sparse_steps;
-    wp.coop_reserve = ss->coop_reserve;
+    wp.sparse_steps = ss->plan.sparse_steps;
+    wp.coop_reserve = ss->plan.coop_reserve;
     // round-queue entries a query wave takes per pull: 32 (64 before round 3's low-chain
     // rounds): a workgroup fills closer to its chain cap in finer pulls; rank-of-1 / 2 / 4 / 8,
     // two calls: +0.5 / +0.5 / +3.5 / +3 % (8 and 16 the same at ranks of 1-4; profiles/r03_lowq)
     wp.batch = (uint32_t)std::min(64, std::max(1, t.batch));
-    wp.end_min = ss->mix[3];
+    wp.end_min = ss->plan.mix[3];
     // aux stack words per query lane (PT_TUNE lstack=N < PT_LSTACK: tests of the exact-DFS
     // hand-over of queries that outgrow it)
     wp.lstack = std::min<uint32_t>(PT_LSTACK, (uint32_t)std::max(1, t.lstack));
@@ -128,14 +128,14 @@ int count_round(pt_session* ss, uint32_t p) {
         HIP_TRY(e);
     }
     HIP_TRY(hipStreamSynchronize(ss->stream));
-    if (ss->ctl_host[pt::C_CARRY] > ss->carry_cap) return fail(PT_E_HIP, "carry queue overflow (a lost chain)");
+    if (ss->ctl_host[pt::C_CARRY] > ss->plan.carry_cap) return fail(PT_E_HIP, "carry queue overflow (a lost chain)");
     return PT_OK;
 }
 
 // ---- diagnostics ---------------------------------------------------------------
 // the per-workgroup profile buffer of cprof / wgprof, its first `bytes` zeroed
 int arm_wg_prof(pt_session* ss, pt::WaveParams& wp, size_t bytes) {
-    if (!ss->wg_prof) HIP_TRY(hipMalloc(&ss->wg_prof, 512ull * ss->path_grid));
+    if (!ss->wg_prof) HIP_TRY(hipMalloc(&ss->wg_prof, 512ull * ss->plan.path_grid));
     HIP_TRY(hipMemsetAsync(ss->wg_prof, 0, bytes, ss->stream));
     wp.wg_prof = ss->wg_prof;
     return PT_OK;
@@ -169,7 +169,7 @@ int report_wgprof(pt_session* ss, const pt::WaveParams& wp, uint32_t p, const ch
     fprintf(stderr, "round %u: in fresh %u carry %u -> out fresh %u carry %u exact %u\n", ss->rounds,
             cnt[0][pt::C_FRESH], cnt[0][pt::C_CARRY], cnt[1][pt::C_FRESH], cnt[1][pt::C_CARRY],
             cnt[1][pt::C_EXACT]);
-    std::vector<unsigned long long> h(64ull * ss->path_grid);
+    std::vector<unsigned long long> h(64ull * ss->plan.path_grid);
     HIP_TRY(hipMemcpyAsync(h.data(), wp.wg_prof, h.size() * 8, hipMemcpyDeviceToHost, ss->stream));
     HIP_TRY(hipStreamSynchronize(ss->stream));
     if (FILE* f = fopen(path, "ab")) {
@@ -185,12 +185,12 @@ int report_round(pt_session* ss, int level, uint32_t target, uint32_t chains, bo
     const double now = wall_ms();
     unsigned long long c[PT_CTR_STRIDE];
     HIP_TRY(read_counters(ss, c));
-    const unsigned long long rays = c[0];
+    const unsigned long long rays = c[pt::CTR_RAYS];
     if (chains) {
         const double ms = now - ss->roundlog_t;
-        const PathShape sh = path_shape(ss, chains, sparse, side);
+        const PathShape sh = path_shape(ss->plan, chains, sparse, side);
         fprintf(stderr, "round %u chains %u -> %u+%u (%s%s, nq %u x %u) %.2f ms rays %llu %.0f Mray/s", ss->rounds, chains,
-                ss->ctl_host[pt::C_FRESH], ss->ctl_host[pt::C_CARRY], chains < ss->lowq ? "low" : "full",
+                ss->ctl_host[pt::C_FRESH], ss->ctl_host[pt::C_CARRY], chains < ss->plan.lowq ? "low" : "full",
                 side ? "+side" : "", sh.nq, sh.grid, ms, rays - ss->roundlog_rays, (rays - ss->roundlog_rays) / ms / 1e3);
         if (level == 3) {
             std::vector<uint4> rec(2ull * ss->n_slots);
@@ -213,7 +213,7 @@ int report_round(pt_session* ss, int level, uint32_t target, uint32_t chains, bo
 int check_dups(pt_session* ss, const pt::WaveParams& wp, uint32_t p, uint32_t chains, bool side) {
     const uint32_t nf = ss->ctl_host[pt::C_FRESH], nc = ss->ctl_host[pt::C_CARRY];
     std::vector<pt::F4> ro(nf);
-    std::vector<uint32_t> cw((size_t)nc * ss->carry_words);
+    std::vector<uint32_t> cw((size_t)nc * ss->plan.carry_words);
     if (nf) HIP_TRY(hipMemcpy(ro.data(), wp.fq[p].ro, nf * sizeof(pt::F4), hipMemcpyDeviceToHost));
     if (nc) HIP_TRY(hipMemcpy(cw.data(), wp.cq[p], cw.size() * 4, hipMemcpyDeviceToHost));
     std::vector<uint8_t> seen(ss->n_slots, 0);
@@ -223,50 +223,50 @@ int check_dups(pt_session* ss, const pt::WaveParams& wp, uint32_t p, uint32_t ch
         if (seen[slot]++) ++dup;
     };
     for (uint32_t i = 0; i < nf; ++i) see(pt::f2u(ro[i].w));
-    for (uint32_t i = 0; i < nc; ++i) see(pt::carry_rec(cw.data(), i, ss->carry_words).slot());
+    for (uint32_t i = 0; i < nc; ++i) see(pt::carry_rec(cw.data(), i, ss->plan.carry_words).slot());
     if (dup || bad)
         fprintf(stderr, "dupcheck: round %u (%s%s) fresh %u carry %u: %u duplicate slot(s), %u out of range\n",
-                ss->rounds, chains < ss->lowq ? "low" : "full", side ? "+side" : "", nf, nc, dup, bad);
+                ss->rounds, chains < ss->plan.lowq ? "low" : "full", side ? "+side" : "", nf, nc, dup, bad);
     return PT_OK;
 }
 
 // ---- the pass's stages ---------------------------------------------------------
 // The final cooperative stage: the cooperative engine runs every remaining chain to the
-// end of the pass.  A launch of teams of 4 (the default) stops once all but ss->coop_grow
+// end of the pass.  A launch of teams of 4 (the default) stops once all but ss->plan.coop_grow
 // of its chains have ended and hands those -- the pass's slowest, whose chain cycle sets
 // the launch's end -- to a launch of whole-wave teams (the shortest cycle).
 // (a scene beyond the engine's LDS tables runs the BIG instantiation: teams of 8 or 64)
 int coop_final(pt_session* ss, const PassTune& t, pt::WaveParams& wp, uint32_t& p, uint32_t chains) {
-    const bool big = coop_big(ss);
-    uint32_t team = big && ss->coop_team != 64u ? 8u : ss->coop_team;
+    const bool big = ss->plan.big;
+    uint32_t team = big && ss->plan.coop_team != 64u ? 8u : ss->plan.coop_team;
     for (;;) {
         // the next stage: teams of 4 or 8 -> (coop_grow_mid, from 8) teams of 32 -> (coop_grow) whole waves
         uint32_t keep = 0u, next_team = 64u;
-        if (team == 8u && !big && ss->coop_grow_mid > ss->coop_grow && chains > ss->coop_grow_mid) {
-            keep = ss->coop_grow_mid;
+        if (team == 8u && !big && ss->plan.coop_grow_mid > ss->plan.coop_grow && chains > ss->plan.coop_grow_mid) {
+            keep = ss->plan.coop_grow_mid;
             next_team = 32u;
-        } else if (team != 64u && ss->coop_grow && chains > ss->coop_grow) {
-            keep = ss->coop_grow;
+        } else if (team != 64u && ss->plan.coop_grow && chains > ss->plan.coop_grow) {
+            keep = ss->plan.coop_grow;
         }
         // (the chains still running at the stop, at most `keep`, go to the next carry
         // queue: never more than it holds)
-        keep = std::min(keep, ss->carry_cap);
+        keep = std::min(keep, ss->plan.carry_cap);
         const bool grow = keep != 0u;
         // (test hook grow_late: its late workgroups hand on every item they find
         // untaken, up to all of the launch's -- within the carry queue only)
         const bool grow_late = grow && t.grow_late;
-        if (grow_late && chains > ss->carry_cap)
+        if (grow_late && chains > ss->plan.carry_cap)
             return fail(PT_E_INVALID, "PT_TUNE grow_late: more chains than the carry queue holds");
         wp.parity = p;
         hipEvent_t i0, i1;
         TRY(launch_events(ss, true, i0, i1));
         HIP_TRY(zero_round_out(ss, p));
         const uint32_t per_wg = QC_WAVES * (64u / team);   // chains per workgroup
-        const uint32_t grid = std::max(1u, std::min(ss->coop_grid, (chains + per_wg - 1u) / per_wg));
+        const uint32_t grid = std::max(1u, std::min(ss->plan.coop_grid, (chains + per_wg - 1u) / per_wg));
         if (t.cprof) TRY(arm_wg_prof(ss, wp, 512));
-        if (ss->coop_order) {
+        if (ss->plan.coop_order) {
             const size_t cap = std::min<size_t>(std::max<size_t>(ss->n_slots, 1),
-                                                std::max<uint32_t>(ss->coop_max, 1u));
+                                                std::max<uint32_t>(ss->plan.coop_max, 1u));
             if (chains > cap) return fail(PT_E_HIP, "cooperative intake order: more chains than entries");
             wp.order_cur = ss->order;
             wp.order = ss->order + 2 * PT_ORDER_BUCKETS;
@@ -315,7 +315,7 @@ struct SideLate {
 // k = the chains it takes (> 0); the round's output set is zero already (zero_round_out)
 int side_launch(pt_session* ss, const PassTune& t, pt::WaveParams& wp, uint32_t p, uint32_t chains, uint32_t k,
                 bool sparse, SideLate& late) {
-    const uint32_t path_grid = path_shape(ss, chains, sparse, true).grid;   // (the round's workgroups: path_round)
+    const uint32_t path_grid = path_shape(ss->plan, chains, sparse, true).grid;   // (the round's workgroups: path_round)
     if (ss->side_th.joinable()) {
         ss->side_th.join();
         if (ss->side_rc != hipSuccess) return fail(PT_E_HIP, "side stream creation failed");
@@ -350,7 +350,7 @@ int side_launch(pt_session* ss, const PassTune& t, pt::WaveParams& wp, uint32_t 
                     (t.handon ? 0u : PT_SIDE_NO_HANDON);
     hipEvent_t i0, i1;
     TRY(launch_events(ss, true, i0, i1));
-    const uint32_t grid = ss->early_wg * (ss->coop_grid / 8u);
+    const uint32_t grid = ss->plan.early_wg * (ss->plan.coop_grid / 8u);
     if (t.side_late) {
         late.on = true;
         late.sp = sp;
@@ -358,7 +358,7 @@ int side_launch(pt_session* ss, const PassTune& t, pt::WaveParams& wp, uint32_t 
         HIP_TRY(hipEventRecord(i0, ss->stream));   // (timed with the round)
         HIP_TRY(hipEventRecord(i1, ss->stream));
     } else {
-        HIP_TRY(pt_launch_coop(sp, grid, ss->side_team, coop_big(ss), ss->side_stream, i0, i1));
+        HIP_TRY(pt_launch_coop(sp, grid, ss->plan.side_team, ss->plan.big, ss->side_stream, i0, i1));
         HIP_TRY(hipEventRecord(ss->side_end, ss->side_stream));
     }
     // the path round takes the other chains: items k .. chains of the order
@@ -369,7 +369,7 @@ int side_launch(pt_session* ss, const PassTune& t, pt::WaveParams& wp, uint32_t 
 }
 int side_launch_late(pt_session* ss, const SideLate& late) {
     // (it yields into the round's output counters, zeroed before the round was enqueued)
-    HIP_TRY(pt_launch_coop(late.sp, late.grid, ss->side_team, coop_big(ss), ss->stream));
+    HIP_TRY(pt_launch_coop(late.sp, late.grid, ss->plan.side_team, ss->plan.big, ss->stream));
     HIP_TRY(hipEventRecord(ss->side_end, ss->stream));
     return PT_OK;
 }
@@ -377,20 +377,20 @@ int side_launch_late(pt_session* ss, const SideLate& late) {
 // one path round (its output set zeroed by the caller): k_wpath -> k_wexact -> k_wshade
 int path_round(pt_session* ss, const PassTune& t, pt::WaveParams& wp, uint32_t p, uint32_t chains, bool sparse) {
     wp.parity = p;
-    if (!t.wgprof.empty()) TRY(arm_wg_prof(ss, wp, 512ull * ss->path_grid));
+    if (!t.wgprof.empty()) TRY(arm_wg_prof(ss, wp, 512ull * ss->plan.path_grid));
     hipEvent_t i0, i1;
     TRY(launch_events(ss, false, i0, i1));
-    const PathShape sh = path_shape(ss, chains, sparse, wp.pin != nullptr);   // (pin: beside the early launch)
-    const bool low = chains < ss->lowq;
-    wp.path_ticks = low ? ss->low_ticks : ss->path_ticks;
-    const uint32_t* m = low ? ss->mix_low : ss->mix;
+    const PathShape sh = path_shape(ss->plan, chains, sparse, wp.pin != nullptr);   // (pin: beside the early launch)
+    const bool low = chains < ss->plan.lowq;
+    wp.path_ticks = low ? ss->plan.low_ticks : ss->plan.path_ticks;
+    const uint32_t* m = low ? ss->plan.mix_low : ss->plan.mix;
     wp.probe_every = m[0];
     wp.probe_min = m[1];
     wp.aux_extra = m[2];
     wp.end_min = m[3];
     // the session's grid of this shape (a low-chain round runs fewer workgroups of it)
-    const uint32_t shape_grid = sh.nq == PT_NQ_BASE ? ss->path_grid : ss->full_grid;
-    wp.path_runend = ss->runend_auto ? shape_grid * sh.nq * 4u : ss->path_runend;
+    const uint32_t shape_grid = sh.nq == PT_NQ_BASE ? ss->plan.path_grid : ss->plan.full_grid;
+    wp.path_runend = ss->plan.runend_auto ? shape_grid * sh.nq * 4u : ss->plan.path_runend;
     // Chains a workgroup may hold: 5/8 of the pixels' fair share, within
     // [256, the shape's capacity].  Below the share, about a third of the chains wait in
     // the queue and go to whichever workgroup drains first, instead of every
@@ -402,7 +402,7 @@ int path_round(pt_session* ss, const PassTune& t, pt::WaveParams& wp, uint32_t p
         const uint64_t share = ((uint64_t)ss->n_slots + shape_grid - 1) / std::max(1u, shape_grid);
         wp.path_cap = (uint32_t)std::min<uint64_t>(sh.cmax, std::max<uint64_t>(256u, share * 5u / 8u));
     }
-    if (low && ss->low_grid) wp.path_cap = sh.cmax;
+    if (low && ss->plan.low_grid) wp.path_cap = sh.cmax;
     if (t.has_cap) wp.path_cap = std::min<uint32_t>(sh.cmax, (uint32_t)std::max(64, t.cap));   // (an explicit cap=N stays)
     HIP_TRY(pt_launch_path_round(wp, sh.nq, sh.grid, 64u, ss->stream, sparse, i0, i1));
     wp.pin = nullptr;   // (only the round beside the early launch skips its chains)
@@ -426,23 +426,23 @@ int trace_wave(pt_session* ss, uint32_t spp) {
     // checked every few rounds (empty rounds are cheap, syncs are not free)
     // (the first round is counted alone: it ends once the pass's work is handed out, and
     // the cooperative engine may take over right after it)
-    uint32_t p = 0, batch = ss->coop_max ? 1u : 4u;
+    uint32_t p = 0, batch = ss->plan.coop_max ? 1u : 4u;
     // end-of-pass kernel when the chains of the last counted round are few; before
     // the first count, the pass's pixels (at most one chain each) decide
-    bool sparse = ss->n_slots < ss->path_sparse;
+    bool sparse = ss->n_slots < ss->plan.path_sparse;
     // the cooperative engine once the chains are few (before the first count: the pixels)
     uint32_t chains = ss->n_slots;
     bool counted = false;
     for (uint32_t guard = 0;; ++guard) {
-        if (chains <= ss->coop_max) {
+        if (chains <= ss->plan.coop_max) {
             TRY(coop_final(ss, t, wp, p, chains));
             break;
         }
         // the early launch's chains
         // (only after a count: before the first one `chains` is the slot count, not the
         // queue's, and every pixel has the same samples left)
-        const bool early = ss->early_k && counted && chains < ss->early_at;
-        const uint32_t k = early ? std::min(ss->early_k, chains / 4u) : 0u;
+        const bool early = ss->plan.early_k && counted && chains < ss->plan.early_at;
+        const uint32_t k = early ? std::min(ss->plan.early_k, chains / 4u) : 0u;
         if (k) batch = 1u;   // (the next round reads what the side launch yields)
         SideLate late;
         for (uint32_t r = 0; r < batch; ++r) {
@@ -464,8 +464,8 @@ int trace_wave(pt_session* ss, uint32_t spp) {
         chains = ss->ctl_host[pt::C_FRESH] + ss->ctl_host[pt::C_CARRY];
         counted = true;
         // near the cooperative hand-over every round is counted (the tail's rounds take ms)
-        batch = chains > 4096u && chains > 4u * ss->coop_max ? ss->round_batch : (chains > 4096u ? 1u : 2u);
-        sparse = chains < ss->path_sparse;
+        batch = chains > 4096u && chains > 4u * ss->plan.coop_max ? ss->plan.round_batch : (chains > 4096u ? 1u : 2u);
+        sparse = chains < ss->plan.path_sparse;
     }
     HIP_TRY(hipEventRecord(e1, ss->stream));
     ss->samples_done += spp;

@@ -66,7 +66,9 @@ int pt_selftest_ray_intersection(pt_scene* s, int32_t traversal, uint32_t n, con
         hits[5 * i + 4] = ok ? (h.interior ? 1.f : 0.f) : 0.f;
     }
     if (counters8) {
-        const uint64_t c[8] = {C.rays, C.nodes, C.ptests, C.planes, C.errs, C.aux, C.fallbacks, 0};
+        uint64_t c[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // (slots CTR_RAYS .. CTR_FALLBACKS_RAY)
+        c[pt::CTR_RAYS] = C.rays; c[pt::CTR_NODES] = C.nodes; c[pt::CTR_PTESTS] = C.ptests; c[pt::CTR_PLANES] = C.planes;
+        c[pt::CTR_ERRORS] = C.errs; c[pt::CTR_AUX] = C.aux; c[pt::CTR_FALLBACKS] = C.fallbacks;
         memcpy(counters8, c, sizeof(c));
     }
     return C.errs ? fail(PT_E_INVALID, "hit list overflow") : PT_OK;

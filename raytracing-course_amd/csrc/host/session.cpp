@@ -1,5 +1,6 @@
 // session.cpp -- tile sessions (pt_session_*): one rank's pixels on one device, their
-// buffers in one allocation, the megakernel pass (exact / division-form traversals),
+// geometry and their buffers in one allocation (both laid out without a device:
+// pt_selftest_wave_plan), the megakernel pass (exact / division-form traversals),
 // the device tonemap with its lost-chain check, statistics, and the tile un-interleave.
 // The wavefront pass itself is rounds.cpp.
 #include <stdio.h>
@@ -105,17 +106,191 @@ pt::SceneView device_view(const pt_scene* s, const DevScene& ds) {
 }
 pt::SceneView device_view(const pt_session* ss) { return device_view(ss->sc, *ss->ds); }
 
-PathShape path_shape(const pt_session* ss, uint32_t chains, bool sparse, bool side) {
-    if (chains < ss->lowq && ss->low_grid) return {PT_NQ_BASE, ss->low_grid, pt::path_cmax(PT_NQ_BASE)};
-    if (sparse || side || ss->full_nq == PT_NQ_BASE) return {PT_NQ_BASE, ss->path_grid, pt::path_cmax(PT_NQ_BASE)};
-    return {ss->full_nq, ss->full_grid, pt::path_cmax(ss->full_nq)};
+// the summed counter block's shared part (a session's and a ray-query context's)
+void counter_stats(const unsigned long long* c, pt_stats* st) {
+    st->rays = c[pt::CTR_RAYS];
+    st->node_visits = c[pt::CTR_NODES];
+    st->prim_tests = c[pt::CTR_PTESTS];
+    st->plane_tests = c[pt::CTR_PLANES];
+    st->errors = c[pt::CTR_ERRORS];
+    st->aux_visits = c[pt::CTR_AUX];
+    st->fallbacks = c[pt::CTR_FALLBACKS];
+    st->fallbacks_ray = c[pt::CTR_FALLBACKS_RAY];
 }
 
-bool coop_big(const pt_session* ss) {
+namespace {
+
+// the Z-order (Morton) code of a tile's coordinates
+uint64_t morton_key(uint32_t tx, uint32_t ty) {
+    uint64_t m = 0;
+    for (int b = 0; b < 16; ++b)
+        m |= (uint64_t)((tx >> b) & 1u) << (2 * b) | (uint64_t)((ty >> b) & 1u) << (2 * b + 1);
+    return m;
+}
+
+// A session's geometry, without a device: the arguments checked, the window, its tiles and the
+// rank's deal of them (tm, gtiles, n_tiles_local, n_slots), the engine, and for the wavefront
+// engine `ord`, the local tiles' seeding order: sorted by the Z-order code of their coordinates
+int session_geometry(pt_scene* s, const pt_session_opts* o, pt_session* ss, std::vector<uint32_t>* ord) {
+    if (!s->prepared) return fail(PT_E_INVALID, "scene not prepared (call pt_scene_prepare)");
+    if (o->world == 0 || o->rank >= o->world) return fail(PT_E_INVALID, "bad rank/world");
+    if (s->hs.W == 0 || s->hs.H == 0) return fail(PT_E_SCENE, "zero image size");
+    if ((uint64_t)s->hs.W * s->hs.H >= 2147483647ull) return fail(PT_E_SCENE, "image too large for per-pixel seeds");
+    // the slot record keeps the current path's vertex count in 24 bits (pt_devutil.h PixelHot)
+    if (s->hs.depth >= (1u << 24)) return fail(PT_E_SCENE, "RAY_DEPTH too large (at most 16777215)");
+    pt::TileMap& tm = ss->tm;
+    tm.W = s->hs.W;
+    tm.H = s->hs.H;
+    tm.x0 = o->win_w ? o->win_x0 : 0u;
+    tm.y0 = o->win_w ? o->win_y0 : 0u;
+    tm.ww = o->win_w ? o->win_w : s->hs.W;
+    tm.wh = o->win_w ? o->win_h : s->hs.H;
+    if (tm.ww == 0 || tm.wh == 0 || (uint64_t)tm.x0 + tm.ww > s->hs.W || (uint64_t)tm.y0 + tm.wh > s->hs.H)
+        return fail(PT_E_INVALID, "window outside the image");
+    tm.tiles_x = (tm.ww + 15u) / 16u;
+    tm.n_tiles = tm.tiles_x * ((tm.wh + 15u) / 16u);
+    tm.rank = o->rank;
+    tm.world = o->world;
+    ss->sc = s;
+    ss->traversal = o->traversal;
+    ss->depth = s->hs.depth;
+    ss->gtiles = rank_tiles(tm.n_tiles, tm.tiles_x, o->rank, o->world);
+    ss->n_tiles_local = (uint32_t)ss->gtiles.size();
+    ss->n_slots = ss->n_tiles_local * 256u;
+    ss->cam = make_cam(s);
+    ss->st.depth = std::max<uint32_t>(ss->depth, 1u);
+    ss->st.n_slots = ss->n_slots;
+    // engine: the wavefront pipeline for the (filtered) replay traversal; the
+    // megakernel for the exact DFS and the division-form replay (PT_TUNE engine=mega forces it)
+    ss->wave = o->traversal == PT_TRAVERSAL_REPLAY && tune_str("engine") != "mega";
+    ord->clear();
+    if (ss->wave) {
+        std::vector<std::pair<uint64_t, uint32_t>> key(ss->n_tiles_local);
+        for (uint32_t t = 0; t < ss->n_tiles_local; ++t)
+            key[t] = {morton_key(ss->gtiles[t] % tm.tiles_x, ss->gtiles[t] / tm.tiles_x), t};
+        std::sort(key.begin(), key.end());
+        for (const auto& k : key) ord->push_back(k.second);
+    }
+    return PT_OK;
+}
+
+// the wavefront pass's plan for this session's pixels and scene on a device of `cus` compute units
+int session_plan(pt_session* ss, uint32_t cus) {
+    if (!ss->wave) return PT_OK;
     const pt_scene* s = ss->sc;
-    return ss->depth > QC_FOLD || s->planes.size() > QC_NPL || s->emitters.size() > QC_NEM;
+    PlanInputs in;
+    in.cus = cus;
+    in.n_slots = ss->n_slots;
+    in.n_tiles_local = ss->n_tiles_local;
+    in.depth = ss->depth;
+    in.n_planes = (uint32_t)s->planes.size();
+    in.n_emitters = (uint32_t)s->emitters.size();
+    in.auxw_stack = s->auxw_stack;
+    in.auxsl_depth = s->auxsl_depth;
+    in.max_stack = s->max_stack;
+    in.n_aux = (uint32_t)s->auxsl.size();
+    return plan_wave(in, &ss->plan);
 }
 
+// Every device buffer of the session in ONE allocation (sections at 256-B offsets): each
+// section is declared once, as the pointer field it fills and its bytes; bind() stores the
+// allocation's base + offset into every field.  `at` is the allocation's size.
+struct Arena {
+    size_t at = 0;
+    std::vector<std::pair<void*, size_t>> fields;   // {the pointer field's address, the section's offset}
+    template <class T>
+    void add(T** field, size_t bytes) {
+        fields.emplace_back((void*)field, at);
+        at = (at + std::max<size_t>(bytes, 16) + 255) & ~(size_t)255;
+    }
+    void bind(unsigned char* base) const {
+        for (const auto& f : fields) {
+            unsigned char* p = base + f.second;
+            memcpy(f.first, &p, sizeof(p));
+        }
+    }
+};
+
+// the session's sections, in the arena's order (`tables`: the tile table, then the seeding order)
+void session_layout(pt_session* ss, size_t n_order, bool fb, uint32_t** tables, Arena& a) {
+    const size_t n = std::max<size_t>(ss->n_slots, 1);
+    const WavePlan& w = ss->plan;
+    a.add(tables, (ss->gtiles.size() + n_order) * 4);
+    a.add(&ss->st.rec, 2 * n * sizeof(uint4));
+    a.add(&ss->st.fold, (size_t)ss->st.depth * n * sizeof(uint4));
+    a.add(&ss->counters, 8 * PT_CTR_COPIES * PT_CTR_STRIDE);
+    a.add(&ss->out, 3 * n);
+    // the window's framebuffer (pt_render's device-side gather; rank 0's session)
+    if (fb) a.add(&ss->fb, 3ull * ss->tm.ww * ss->tm.wh);
+    if (!ss->wave) return;
+    for (pt::RayQ& q : ss->fq) {
+        a.add(&q.ro, n * 16);
+        a.add(&q.rd, n * 16);
+        a.add(&q.ri, n * 16);
+    }
+    a.add(&ss->fq[0].pid, 2 * n * 4);   // (both queues' halves: fq[1].pid is fq[0].pid + n)
+    a.add(&ss->done.ro, n * 16);
+    a.add(&ss->ex.ro, n * 16);
+    a.add(&ss->done.rd, n * 16);
+    a.add(&ss->ex.rd, n * 16);
+    a.add(&ss->done.id, n * 4);
+    a.add(&ss->carry, 2ull * w.carry_cap * w.carry_words * 4);
+    a.add(&ss->ctl, 8 * PT_CTL_SET);
+    a.add(&ss->endq, std::max((size_t)w.path_grid * pt::path_cmax(PT_NQ_BASE),
+                              (size_t)w.full_grid * pt::path_cmax(w.full_nq)) * sizeof(uint2));
+    a.add(&ss->order, (n + 2 * PT_ORDER_BUCKETS) * 4);
+    if (w.early_k) {
+        a.add(&ss->side.ro, (size_t)w.early_k * 16);
+        a.add(&ss->side.rd, (size_t)w.early_k * 16);
+        a.add(&ss->side.ri, (size_t)w.early_k * 16);
+        a.add(&ss->side.pid, (size_t)w.early_k * 4);
+        a.add(&ss->side_carry, (size_t)w.early_k * w.carry_words * 4);
+        a.add(&ss->side_ctl, 8 * PT_CTL_SET);
+    }
+}
+
+// the early launch's stream and events: made on a helper thread beside the set-up and
+// the pass's first rounds (a stream's creation costs ~10 ms: neither on the set-up's
+// path nor in the pass), joined where the first early launch needs them
+int start_side_stream(pt_session* ss) {
+    const int dev = ss->dev;
+    auto make = [ss, dev] {
+        ss->side_rc = hipSetDevice(dev);
+        if (ss->side_rc == hipSuccess) ss->side_rc = take_stream(dev, &ss->side_stream, true);
+        if (ss->side_rc == hipSuccess) ss->side_rc = hipEventCreateWithFlags(&ss->side_taken, hipEventDisableTiming);
+        if (ss->side_rc == hipSuccess) ss->side_rc = hipEventCreateWithFlags(&ss->side_end, hipEventDisableTiming);
+    };
+    try {
+        ss->side_th = std::thread(make);
+    } catch (const std::system_error&) {
+        // (no helper thread: made here, and the current device set back)
+        make();
+        if (hipSetDevice(ss->dev) != hipSuccess) return fail(PT_E_HIP, "hipSetDevice failed");
+    }
+    return PT_OK;
+}
+
+// a rank's packed tiles (256 pixels of 3 T each) scattered into the W x H image
+template <class T>
+int unpack_tiles(uint32_t W, uint32_t H, uint32_t rank, uint32_t world, const T* packed, T* img) {
+    if (!packed || !img || world == 0) return fail(PT_E_INVALID, "bad argument");
+    const uint32_t tiles_x = (W + 15u) / 16u, n_tiles = tiles_x * ((H + 15u) / 16u);
+    uint32_t lt = 0;
+    for (uint32_t gt = 0; gt < n_tiles; ++gt) {
+        if (pt::tile_owner(gt, tiles_x, world) != rank) continue;
+        const uint32_t tx = gt % tiles_x, ty = gt / tiles_x;
+        for (uint32_t j = 0; j < 16u; ++j) {
+            const uint32_t y = ty * 16u + j;
+            if (y >= H) break;
+            const uint32_t x0 = tx * 16u, w = std::min(16u, W - x0);
+            memcpy(img + ((size_t)y * W + x0) * 3, packed + ((size_t)lt * 256u + j * 16u) * 3, (size_t)w * 3 * sizeof(T));
+        }
+        ++lt;
+    }
+    return PT_OK;
+}
+
+}  // namespace
 }  // namespace pti
 
 using namespace pti;
@@ -125,45 +300,19 @@ extern "C" {
 // ------------------------------------------------------------- sessions ---
 int pt_session_create(pt_scene* s, const pt_session_opts* o, pt_session** out) {
     if (!s || !o || !out) return fail(PT_E_INVALID, "null argument");
-    if (!s->prepared) return fail(PT_E_INVALID, "scene not prepared (call pt_scene_prepare)");
-    if (o->world == 0 || o->rank >= o->world) return fail(PT_E_INVALID, "bad rank/world");
-    if (s->hs.W == 0 || s->hs.H == 0) return fail(PT_E_SCENE, "zero image size");
-    if ((uint64_t)s->hs.W * s->hs.H >= 2147483647ull) return fail(PT_E_SCENE, "image too large for per-pixel seeds");
-    // the slot record keeps the current path's vertex count in 24 bits (pt_devutil.h PixelHot)
-    if (s->hs.depth >= (1u << 24)) return fail(PT_E_SCENE, "RAY_DEPTH too large (at most 16777215)");
-    int rc = check_device(o->device);
-    if (rc) return rc;
-    // the megakernel (exact / division-form traversal, PT_TUNE engine=mega) also reads the BVH2 aux
-    const bool mega = o->traversal != PT_TRAVERSAL_REPLAY || tune_str("engine") == "mega";
-    DevScene* ds = nullptr;
-    double up_ms = 0.0;
-    if ((rc = ensure_device_scene(s, o->device, mega, &ds, &up_ms))) return rc;
     auto* ss = new pt_session();
-    ss->sc = s;
+    std::vector<uint32_t> ord;   // wavefront: the local tiles' seeding order
+    int rc = session_geometry(s, o, ss, &ord);
+    if (!rc) rc = check_device(o->device);
+    // the megakernel (exact / division-form traversal, PT_TUNE engine=mega) also reads the BVH2 aux
+    DevScene* ds = nullptr;
+    if (!rc) rc = ensure_device_scene(s, o->device, !ss->wave, &ds, &ss->upload_ms);
+    if (rc) {
+        delete ss;   // (nothing on a device yet)
+        return rc;
+    }
     ss->dev = o->device;
     ss->ds = ds;
-    ss->upload_ms = up_ms;
-    ss->traversal = o->traversal;
-    ss->depth = s->hs.depth;
-    ss->tm.W = s->hs.W;
-    ss->tm.H = s->hs.H;
-    ss->tm.x0 = o->win_w ? o->win_x0 : 0u;
-    ss->tm.y0 = o->win_w ? o->win_y0 : 0u;
-    ss->tm.ww = o->win_w ? o->win_w : s->hs.W;
-    ss->tm.wh = o->win_w ? o->win_h : s->hs.H;
-    if (ss->tm.ww == 0 || ss->tm.wh == 0 || (uint64_t)ss->tm.x0 + ss->tm.ww > s->hs.W ||
-        (uint64_t)ss->tm.y0 + ss->tm.wh > s->hs.H) {
-        delete ss;
-        return fail(PT_E_INVALID, "window outside the image");
-    }
-    ss->tm.tiles_x = (ss->tm.ww + 15u) / 16u;
-    ss->tm.n_tiles = ss->tm.tiles_x * ((ss->tm.wh + 15u) / 16u);
-    ss->tm.rank = o->rank;
-    ss->tm.world = o->world;
-    ss->gtiles = rank_tiles(ss->tm.n_tiles, ss->tm.tiles_x, o->rank, o->world);
-    ss->n_tiles_local = (uint32_t)ss->gtiles.size();
-    ss->n_slots = ss->n_tiles_local * 256u;
-    ss->cam = make_cam(s);
     auto cleanup = [&](int code) {
         pt_session_free(ss);
         return code;
@@ -171,271 +320,30 @@ int pt_session_create(pt_scene* s, const pt_session_opts* o, pt_session** out) {
     if (hipSetDevice(ss->dev) != hipSuccess) return cleanup(fail(PT_E_HIP, "hipSetDevice failed"));
     DevProps props;
     if ((rc = device_props(ss->dev, &props))) return cleanup(rc);
-    const uint32_t cus = (uint32_t)props.cus;
-    const size_t n = std::max<size_t>(ss->n_slots, 1);
-    ss->st.depth = std::max<uint32_t>(ss->depth, 1u);
-    ss->st.n_slots = ss->n_slots;
-    // engine: the wavefront pipeline for the (filtered) replay traversal; the
-    // megakernel for the exact DFS and the division-form replay (PT_TUNE engine=mega forces it)
-    ss->wave = o->traversal == PT_TRAVERSAL_REPLAY;
-    if (tune_str("engine") == "mega") ss->wave = false;
-    std::vector<uint32_t> ord;   // wavefront: the local tiles' seeding order
-    if (ss->wave) {
-        ss->shade_grid = std::min<uint32_t>(cus * 8u, std::max(1u, ss->n_tiles_local));
-        // path engine: NQ query waves + 1 shade wave per workgroup, as many workgroups
-        // per CU as its waves-per-SIMD occupancy holds (4 SIMDs per CU)
-        ss->path_budget = (uint32_t)std::max(1, tune_int("budget", (int)ss->path_budget));
-        // rounds end at one time for every wave (budget_us after the work ran out; 0: each
-        // wave after `budget` trips of its own, also the mode of an explicit budget=N alone)
-        // (at most 10 s: the device compares 32-bit clock differences as signed)
-        ss->path_ticks = (uint32_t)std::min(10000000, std::max(0, tune_int("budget_us", tune_has("budget") ? 0 : 2500))) * 100u;
-        // ... and the low-chain rounds' deadline: 5 ms (fewer rounds, each of which re-sorts and
-        // re-takes the early launch's heaviest chains; with coop_grow 16 per CU, one GPU call,
-        // 3 repeats of every rank (tools/gpu_r5_ab.sh, profiles/r05_ab): rank of 8 mean 83.5 ->
-        // 80.2 ms per 256-spp pass, rank of 4 139.9 -> 137.6, of 2 259.2 -> 255.6, one GPU
-        // 488.8 -> 486.3); with budget_us=0 (trip budgets) the path rounds' mode
-        // (lowq_budget_us=0: trip budgets in those rounds, as budget_us=0 for every round)
-        ss->low_ticks = tune_has("lowq_budget_us")
-                            ? (uint32_t)std::min(10000000, std::max(0, tune_int("lowq_budget_us", 5000))) * 100u
-                            : ss->path_ticks == 0 ? 0u : 500000u;
-        // (the full rounds' shape, PT_TUNE nq: 2, or 3 query waves per shade wave at 3 workgroups per CU)
-        if (tune_has("nq")) {
-            const std::string v = tune_str("nq");
-            if (v != "2" && v != "3")
-                return cleanup(fail(PT_E_INVALID, "PT_TUNE nq=" + v + ": no such shape (2 or 3 query waves per workgroup)"));
-            ss->full_nq = v == "3" ? 3u : 2u;
-        }
-        ss->path_grid = cus * (uint32_t)std::max(1, tune_int("wg_per_cu", (int)pt::path_wg_per_cu(PT_NQ_BASE)));
-        ss->full_grid = cus * (uint32_t)std::max(1, tune_int("wg_per_cu", (int)pt::path_wg_per_cu(ss->full_nq)));
-        // the query lanes of the larger launch
-        const uint64_t lanes = std::max<uint64_t>((uint64_t)ss->path_grid * PT_NQ_BASE, (uint64_t)ss->full_grid * ss->full_nq) * 64u;
-        // suspended-query records (pt_kernels.h CarryRec: Query | slot | aux stack).  Only a
-        // query lane suspends (one query at round end), and a pixel has at most one ray
-        // in flight, so a round appends at most min(pixels, query lanes) of them: the
-        // carry queue can never overflow.  The exact-DFS hand-over queues (ex, done, hid)
-        // do NOT have that bound: a lane that hands its ray over goes on with another
-        // chain of the round's supply, so a round can hand over a ray of every chain --
-        // at most one per pixel (a chain that leaves for k_wexact leaves the round).
-        // They hold n entries.
-        ss->carry_words = pt::carry_record_words(std::max<uint32_t>(s->auxw_stack, 1u));
-        ss->lane_cap = (uint32_t)std::min<uint64_t>(n, lanes);
-        ss->carry_cap = ss->lane_cap;
-        // a round whose chains are this few runs them to the end of the pass (a few
-        // per query wave of its launch, 4: rebalancing them costs more rounds than it saves)
-        ss->runend_auto = !tune_has("runend");
-        ss->path_runend = (uint32_t)std::max(0, tune_int("runend", 0));
-        // rounds with fewer chains than this run the end-of-pass (sparse) kernel (its own shape's lanes)
-        ss->path_sparse = ss->path_grid * PT_NQ_BASE * 32u;
-        ss->path_sparse = (uint32_t)std::max(0, tune_int("sparse", (int)ss->path_sparse));
-        ss->sparse_steps = (uint32_t)std::max(1, tune_int("sparse_steps", (int)ss->sparse_steps));
-        // a round whose chains are at most this many runs the cooperative engine (one
-        // wave per chain) to the end of the pass; it needs a wave's aux stack to hold
-        // a depth-first descent below its expansion limit, and lane 0's exact DFS stack
-        // 49,152 on the 256-CU part (2 query waves per shade wave, hit-region query; rank-of-4 /
-        // rank-of-8 per GPU, teams of 8, two runs each: 32 k 2,758-2,782 / 2,348-2,396, 49 k
-        // 2,754-2,774 / 2,377-2,421, 65 k 2,731-2,763 / 2,318-2,338, 98 k 2,695-2,699 / 2,220-2,324,
-        // 131 k 2,599-2,603 / 2,358-2,430 Mray/s)
-        ss->coop_max = cus * 192u;
-        ss->coop_max = (uint32_t)std::max(0, tune_int("coop", (int)ss->coop_max));
-        ss->coop_grid = cus * 8u;
-        // (a depth-first descent below the expansion limit adds at most 3 entries per level)
-        const uint32_t reserve = 3u * (s->auxsl_depth + 2u);
-        // a team size's stacks hold this tree (the engine's capacities: pt_kernels.h qc_*): the
-        // expansion (its own stack, or for teams of 4 the wave's pool) a depth-first descent
-        // below the reserve, and the leader's exact DFS (its stack, or its slice of the pool)
-        // the whole tree (and for teams below 64 the pool's items, chain << shift | node, hold
-        // every aux entry index)
-        auto stack_ok = [&](uint32_t expand, uint32_t dfs) { return expand >= reserve + 64u && s->max_stack <= dfs; };
-        auto team_ok = [&](uint32_t t) {
-            if (t < 64u && s->auxsl.size() >= (1ull << pt::qc_item_shift(t))) return false;
-            return stack_ok(t == 4u ? pt::qc_pool_words(t) : pt::qc_stack_words(t), pt::qc_stack_words(t));
-        };
-        ss->coop_team = (uint32_t)tune_int("coop_team", (int)ss->coop_team);
-        if (ss->coop_team != 4u && ss->coop_team != 8u && ss->coop_team != 16u && ss->coop_team != 32u)
-            ss->coop_team = 64u;
-        if (!team_ok(ss->coop_team)) ss->coop_team = 64u;   // deep trees: whole-wave teams
-        // (paths deeper than QC_FOLD keep their further fold records in HBM, planes and
-        // emitters beyond QC_NPL / QC_NEM come from HBM: no scene limit besides the stacks)
-        if (!stack_ok(pt::qc_stack_words(64u), pt::qc_stack_words(64u)))
-            ss->coop_max = 0;
-        else ss->coop_reserve = reserve;
-        // with the cooperative engine the path engine never runs a round to the end:
-        // its rounds stay budget-limited, so the host sees the chains fall below coop_max
-        if (ss->coop_max && ss->runend_auto) {
-            ss->path_runend = 0;
-            ss->runend_auto = false;
-        }
-        // ... and the end-of-pass (sparse) path kernel, whose rounds are long, never runs
-        // above the hand-over
-        if (ss->coop_max && !tune_has("sparse")) ss->path_sparse = std::min(ss->path_sparse, ss->coop_max);
-        ss->round_batch = (uint32_t)std::max(1, tune_int("round_batch", (int)ss->round_batch));
-        ss->coop_order = tune_int("coop_order", 1) != 0;
-        // the final launch's last chains to whole-wave teams: 16 per CU (4 per CU measured within
-        // the spread of 0; 16 with the 5-ms low-round deadline above: see low_ticks)
-        ss->coop_grow = (uint32_t)std::max(0, tune_int("coop_grow", (int)(cus * 16u)));
-        // ... and, before that, its last coop_grow_mid chains to teams of 32 (0: no such stage; a
-        // tree too deep for the teams-of-32 stack skips it)
-        ss->coop_grow_mid = (uint32_t)std::max(0, tune_int("coop_grow_mid", 0));
-        if (!stack_ok(pt::qc_stack_words(32u), pt::qc_stack_words(32u))) ss->coop_grow_mid = 0u;
-        // Early cooperative launch (teams of side_team lanes, QC_WAVES waves per workgroup):
-        // the low-chain rounds leave each CU room for one more workgroup, which the heaviest
-        // chains use from then on instead of waiting for the final hand-over
-        ss->early_wg = (uint32_t)std::max(1, tune_int("early_wg", 1));
-        ss->early_at = (uint32_t)std::max(0, tune_int("early_at", (int)(cus * 768u)));
-        ss->early_k = (uint32_t)std::max(0, tune_int("early", 1));
-        // lanes per chain of that launch: 4 (default: 16 chains per wave, its pooled query keeps
-        // a wave's lanes busy with half as many lanes per chain; rank 0 of 8 73.5-75.2 ms against
-        // 76.4-83.1 with teams of 8, of 4 130.4-132.0 against 131.1-133.7, of 1 472-476 against
-        // 476-480: profiles/r06_coop/team4), 8, 16, 32 or 64
-        // (a scene beyond the LDS tables has only the teams-of-8 BIG instantiation)
-        const bool big = coop_big(ss);
-        {
-            const int st = tune_int("side_team", 4);
-            ss->side_team = !big && (st == 4 || st == 16 || st == 32 || st == 64) ? (uint32_t)st : 8u;
-            if (!team_ok(ss->side_team)) ss->side_team = team_ok(8u) ? 8u : 64u;
-        }
-        if (ss->early_k == 1u) ss->early_k = cus * ss->early_wg * QC_WAVES * (64u / ss->side_team);   // early=1: what it holds
-        if (!ss->coop_max || (ss->coop_team != 8u && ss->coop_team != 4u) || ss->side_team == 64u) ss->early_k = 0;
-        // a round's carry output also takes the early launch's yielded chains
-        ss->carry_cap = (uint32_t)std::min<uint64_t>(n, (uint64_t)ss->lane_cap + ss->early_k);
-        {
-            static const char* keys[4] = {"probe_every", "probe_min", "aux_extra", "end_min"};
-            static const char* lkeys[4] = {"lowq_probe_every", "lowq_probe_min", "lowq_aux_extra", "lowq_end_min"};
-            for (int i = 0; i < 4; ++i) {
-                const int lo = i == 0 || i == 3 ? 1 : 0;
-                ss->mix[i] = (uint32_t)std::max(lo, tune_int(keys[i], (int)ss->mix[i]));
-                // (the low rounds' end_min has a default of its own; the others follow the full rounds')
-                ss->mix_low[i] = (uint32_t)std::max(lo, tune_int(lkeys[i], (int)(i == 3 ? ss->mix_low[i] : ss->mix[i])));
-            }
-            ss->mix[3] = std::min<uint32_t>(ss->mix[3], 64u);
-            ss->mix_low[3] = std::min<uint32_t>(ss->mix_low[3], 64u);
-            // Rounds that start with fewer than 768 chains per CU run on 2 path workgroups
-            // per CU (PT_CMAX chains each) instead of 4: with that few chains the rounds are
-            // bound by each chain's latency, and a query trip's instruction stream shares its
-            // SIMD with fewer waves.  Rank-of-1 / 2 / 4 / 8 (rank 0, three interleaved
-            // repeats, profiles/r03_lowq): +2.3 / +2 / +4 / +3-10 %; 150 k / 250 k chains
-            // within 1 % at ranks of 1-4, and 300 k (every round of a rank of 8, the first
-            // included) -25 % at rank-of-8.
-            ss->lowq = (uint32_t)std::max(0, tune_int("lowq", (int)(cus * 768u)));
-            ss->low_grid = std::min(ss->path_grid, cus * (uint32_t)std::max(1, tune_int("lowq_wg", 2)));
-        }
-        if (ss->n_tiles_local) {
-            // seeding order of the pass: the local tiles sorted by the Z-order (Morton)
-            // code of their tile coordinates
-            std::vector<std::pair<uint64_t, uint32_t>> key(ss->n_tiles_local);
-            for (uint32_t t = 0; t < ss->n_tiles_local; ++t) {
-                const uint32_t gt = ss->gtiles[t];
-                const uint32_t tx = gt % ss->tm.tiles_x, ty = gt / ss->tm.tiles_x;
-                uint64_t m = 0;
-                for (int b = 0; b < 16; ++b)
-                    m |= (uint64_t)((tx >> b) & 1u) << (2 * b) | (uint64_t)((ty >> b) & 1u) << (2 * b + 1);
-                key[t] = {m, t};
-            }
-            std::sort(key.begin(), key.end());
-            ord.resize(ss->n_tiles_local);
-            for (uint32_t t = 0; t < ss->n_tiles_local; ++t) ord[t] = key[t].second;
-        }
+    if ((rc = session_plan(ss, (uint32_t)props.cus))) return cleanup(rc);
+    if (take_stream(ss->dev, &ss->stream) != hipSuccess) return cleanup(fail(PT_E_HIP, "stream creation failed"));
+    if (ss->plan.early_k && (rc = start_side_stream(ss))) return cleanup(rc);
+    // the arena, and the two small host-made tables with one copy: session set-up is a
+    // handful of runtime calls, whatever the pixel count
+    Arena arena;
+    uint32_t* tables = nullptr;
+    session_layout(ss, ord.size(), o->rank == 0, &tables, arena);
+    void* p = nullptr;
+    if (hipMalloc(&p, arena.at) != hipSuccess) return cleanup(fail(PT_E_OOM, "device allocation failed (session buffers)"));
+    ss->arena = static_cast<unsigned char*>(p);
+    ss->arena_bytes = arena.at;
+    arena.bind(ss->arena);
+    if (ss->wave) ss->fq[1].pid = ss->fq[0].pid + std::max<size_t>(ss->n_slots, 1);
+    if (!ss->gtiles.empty()) {
+        std::vector<uint32_t> t(ss->gtiles);
+        t.insert(t.end(), ord.begin(), ord.end());
+        if (hipMemcpy(tables, t.data(), t.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+            return cleanup(fail(PT_E_HIP, "tile tables upload failed"));
+        ss->tm.gtile = tables;
+        if (!ord.empty()) ss->tile_order = tables + ss->gtiles.size();
     }
-    // Every device buffer of the session in ONE allocation (sections at 256-B
-    // offsets), and the two small host-made tables with one copy: session set-up is
-    // a handful of runtime calls, whatever the pixel count.
-    {
-        size_t at = 0;
-        auto sec = [&at](size_t bytes) {
-            const size_t o = at;
-            at = (at + std::max<size_t>(bytes, 16) + 255) & ~(size_t)255;
-            return o;
-        };
-        const size_t tables = sec((ss->gtiles.size() + ord.size()) * 4);
-        const size_t a_rec = sec(2 * n * sizeof(uint4)), a_fold = sec((size_t)ss->st.depth * n * sizeof(uint4));
-        const size_t a_ctr = sec(8 * PT_CTR_COPIES * PT_CTR_STRIDE), a_out = sec(3 * n);
-        // the window's framebuffer (pt_render's device-side gather; rank 0's session)
-        const size_t a_fb = o->rank == 0 ? sec(3ull * ss->tm.ww * ss->tm.wh) : 0;
-        size_t a_fq[2][3] = {{0, 0, 0}, {0, 0, 0}}, a_pid = 0, a_dq[2] = {0, 0}, a_ex[2] = {0, 0}, a_hid = 0;
-        size_t a_carry = 0, a_ctl = 0, a_endq = 0, a_order = 0, a_side[6] = {0, 0, 0, 0, 0, 0};
-        if (ss->wave) {
-            for (int q = 0; q < 2; ++q)
-                for (int k = 0; k < 3; ++k) a_fq[q][k] = sec(n * 16);
-            a_pid = sec(2 * n * 4);
-            for (int k = 0; k < 2; ++k) { a_dq[k] = sec(n * 16); a_ex[k] = sec(n * 16); }
-            a_hid = sec(n * 4);
-            a_carry = sec(2ull * ss->carry_cap * ss->carry_words * 4);
-            a_ctl = sec(8 * PT_CTL_SET);
-            a_endq = sec(std::max((size_t)ss->path_grid * pt::path_cmax(PT_NQ_BASE),
-                                  (size_t)ss->full_grid * pt::path_cmax(ss->full_nq)) * sizeof(uint2));
-            a_order = sec((n + 2 * PT_ORDER_BUCKETS) * 4);
-            if (ss->early_k) {
-                for (int k = 0; k < 3; ++k) a_side[k] = sec((size_t)ss->early_k * 16);
-                a_side[3] = sec((size_t)ss->early_k * 4);
-                a_side[4] = sec((size_t)ss->early_k * ss->carry_words * 4);
-                a_side[5] = sec(8 * PT_CTL_SET);
-            }
-        }
-        if (take_stream(ss->dev, &ss->stream) != hipSuccess) return cleanup(fail(PT_E_HIP, "stream creation failed"));
-        // the early launch's stream and events: made on a helper thread beside the set-up and
-        // the pass's first rounds (a stream's creation costs ~10 ms: neither on the set-up's
-        // path nor in the pass), joined where the first early launch needs them
-        if (ss->early_k) {
-            const int dev = ss->dev;
-            auto make = [ss, dev] {
-                ss->side_rc = hipSetDevice(dev);
-                if (ss->side_rc == hipSuccess) ss->side_rc = take_stream(dev, &ss->side_stream, true);
-                if (ss->side_rc == hipSuccess) ss->side_rc = hipEventCreateWithFlags(&ss->side_taken, hipEventDisableTiming);
-                if (ss->side_rc == hipSuccess) ss->side_rc = hipEventCreateWithFlags(&ss->side_end, hipEventDisableTiming);
-            };
-            try {
-                ss->side_th = std::thread(make);
-            } catch (const std::system_error&) {
-                // (no helper thread: made here, and the current device set back)
-                make();
-                if (hipSetDevice(ss->dev) != hipSuccess) return cleanup(fail(PT_E_HIP, "hipSetDevice failed"));
-            }
-        }
-        void* p = nullptr;
-        if (hipMalloc(&p, at) != hipSuccess) return cleanup(fail(PT_E_OOM, "device allocation failed (session buffers)"));
-        ss->arena = static_cast<unsigned char*>(p);
-        unsigned char* A = ss->arena;
-        if (!ss->gtiles.empty()) {
-            std::vector<uint32_t> t(ss->gtiles);
-            t.insert(t.end(), ord.begin(), ord.end());
-            if (hipMemcpy(A + tables, t.data(), t.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-                return cleanup(fail(PT_E_HIP, "tile tables upload failed"));
-            ss->tm.gtile = reinterpret_cast<const uint32_t*>(A + tables);
-            if (!ord.empty()) ss->tile_order = reinterpret_cast<uint32_t*>(A + tables) + ss->gtiles.size();
-        }
-        ss->st.rec = reinterpret_cast<uint4*>(A + a_rec);
-        ss->st.fold = reinterpret_cast<uint4*>(A + a_fold);
-        ss->counters = reinterpret_cast<unsigned long long*>(A + a_ctr);
-        ss->out = A + a_out;
-        if (o->rank == 0) ss->fb = A + a_fb;
-        if (ss->wave) {
-            for (int q = 0; q < 2; ++q) {
-                ss->fq[q].ro = reinterpret_cast<pt::F4*>(A + a_fq[q][0]);
-                ss->fq[q].rd = reinterpret_cast<pt::F4*>(A + a_fq[q][1]);
-                ss->fq[q].ri = reinterpret_cast<pt::F4*>(A + a_fq[q][2]);
-                ss->fq[q].pid = reinterpret_cast<int*>(A + a_pid) + q * n;
-            }
-            ss->done = pt::DoneQ{reinterpret_cast<pt::F4*>(A + a_dq[0]), reinterpret_cast<pt::F4*>(A + a_dq[1]),
-                                 reinterpret_cast<uint32_t*>(A + a_hid)};
-            ss->ex = pt::RayQ{reinterpret_cast<pt::F4*>(A + a_ex[0]), reinterpret_cast<pt::F4*>(A + a_ex[1]), nullptr,
-                              nullptr};
-            ss->carry = reinterpret_cast<uint32_t*>(A + a_carry);
-            ss->ctl = reinterpret_cast<uint32_t*>(A + a_ctl);
-            ss->endq = reinterpret_cast<uint2*>(A + a_endq);
-            ss->order = reinterpret_cast<uint32_t*>(A + a_order);
-            if (ss->early_k) {
-                ss->side.ro = reinterpret_cast<pt::F4*>(A + a_side[0]);
-                ss->side.rd = reinterpret_cast<pt::F4*>(A + a_side[1]);
-                ss->side.ri = reinterpret_cast<pt::F4*>(A + a_side[2]);
-                ss->side.pid = reinterpret_cast<int*>(A + a_side[3]);
-                ss->side_carry = reinterpret_cast<uint32_t*>(A + a_side[4]);
-                ss->side_ctl = reinterpret_cast<uint32_t*>(A + a_side[5]);
-            }
-            if (hipHostMalloc(&ss->ctl_host, 64) != hipSuccess)
-                return cleanup(fail(PT_E_OOM, "host allocation failed (round counters)"));
-        }
-        ss->arena_bytes = at;
-    }
+    if (ss->wave && hipHostMalloc(&ss->ctl_host, 64) != hipSuccess)
+        return cleanup(fail(PT_E_OOM, "host allocation failed (round counters)"));
     if (hipMemsetAsync(ss->counters, 0, 8 * PT_CTR_COPIES * PT_CTR_STRIDE, ss->stream) != hipSuccess) return cleanup(fail(PT_E_HIP, "memset failed"));
     if (ss->n_tiles_local) {
         pt::InitParams ip;
@@ -445,6 +353,27 @@ int pt_session_create(pt_scene* s, const pt_session_opts* o, pt_session** out) {
             return cleanup(fail(PT_E_HIP, "k_init launch failed"));
     }
     *out = ss;
+    return PT_OK;
+}
+
+// test hook: a session's geometry, plan and arena layout for a device of `cus` compute units,
+// as "key=value" lines (no device needed; o->device is ignored)
+int pt_selftest_wave_plan(pt_scene* s, const pt_session_opts* o, uint32_t cus, char* buf, size_t cap) {
+    if (!s || !o || !buf) return fail(PT_E_INVALID, "null argument");
+    int rc = pt_scene_prepare(s);
+    if (rc) return rc;
+    pt_session ss;
+    std::vector<uint32_t> ord;
+    if ((rc = session_geometry(s, o, &ss, &ord))) return rc;
+    if ((rc = session_plan(&ss, cus))) return rc;
+    Arena arena;
+    uint32_t* tables = nullptr;
+    session_layout(&ss, ord.size(), o->rank == 0, &tables, arena);
+    const std::string t = plan_text(ss.plan) + "n_slots=" + std::to_string(ss.n_slots) + "\nn_tiles_local=" +
+                          std::to_string(ss.n_tiles_local) + "\narena_bytes=" + std::to_string(arena.at) +
+                          "\naux_stack_words=" + std::to_string(s->auxw_stack) + "\n";
+    if (t.size() + 1 > cap) return fail(PT_E_INVALID, "buffer too small");
+    memcpy(buf, t.c_str(), t.size() + 1);
     return PT_OK;
 }
 
@@ -607,14 +536,7 @@ int pt_session_stats(pt_session* ss, pt_stats* st) {
     unsigned long long c[PT_CTR_STRIDE];
     HIP_TRY(read_counters(ss, c));
     memset(st, 0, sizeof(*st));
-    st->rays = c[0];
-    st->node_visits = c[1];
-    st->prim_tests = c[2];
-    st->plane_tests = c[3];
-    st->errors = c[4];
-    st->aux_visits = c[5];
-    st->fallbacks = c[6];
-    st->fallbacks_ray = c[7];
+    counter_stats(c, st);
     st->samples = owned_pixels(ss) * ss->samples_done;
     st->kernel_ms = ss->kernel_ms;
     st->resolve_ms = ss->resolve_ms;
@@ -628,10 +550,10 @@ int pt_session_stats(pt_session* ss, pt_stats* st) {
     st->isect_ms = ss->isect_ms;
     st->isect_launches = ss->isect_launches;
     st->rounds = ss->rounds;
-    st->coop_rays = c[8];
-    st->coop_node_visits = c[9];
-    st->coop_prim_tests = c[10];
-    st->coop_aux_visits = c[13];
+    st->coop_rays = c[pt::CTR_COOP_RAYS];
+    st->coop_node_visits = c[pt::CTR_COOP_NODES];
+    st->coop_prim_tests = c[pt::CTR_COOP_PTESTS];
+    st->coop_aux_visits = c[pt::CTR_COOP_AUX];
     st->coop_ms = ss->coop_ms;
     st->coop_launches = ss->coop_launches;
     st->short_pixels = c[pt::CTR_SHORT];
@@ -668,39 +590,11 @@ void pt_session_free(pt_session* ss) {
 }
 
 int pt_unpack_tiles(uint32_t W, uint32_t H, uint32_t rank, uint32_t world, const uint8_t* packed, uint8_t* rgb) {
-    if (!packed || !rgb || world == 0) return fail(PT_E_INVALID, "bad argument");
-    const uint32_t tiles_x = (W + 15u) / 16u, n_tiles = tiles_x * ((H + 15u) / 16u);
-    uint32_t lt = 0;
-    for (uint32_t gt = 0; gt < n_tiles; ++gt) {
-        if (pt::tile_owner(gt, tiles_x, world) != rank) continue;
-        const uint32_t tx = gt % tiles_x, ty = gt / tiles_x;
-        for (uint32_t j = 0; j < 16u; ++j) {
-            const uint32_t y = ty * 16u + j;
-            if (y >= H) break;
-            const uint32_t x0 = tx * 16u, w = std::min(16u, W - x0);
-            memcpy(rgb + ((size_t)y * W + x0) * 3, packed + ((size_t)lt * 256u + j * 16u) * 3, (size_t)w * 3);
-        }
-        ++lt;
-    }
-    return PT_OK;
+    return unpack_tiles<uint8_t>(W, H, rank, world, packed, rgb);
 }
 
 int pt_unpack_tiles_f32(uint32_t W, uint32_t H, uint32_t rank, uint32_t world, const float* packed, float* rad) {
-    if (!packed || !rad || world == 0) return fail(PT_E_INVALID, "bad argument");
-    const uint32_t tiles_x = (W + 15u) / 16u, n_tiles = tiles_x * ((H + 15u) / 16u);
-    uint32_t lt = 0;
-    for (uint32_t gt = 0; gt < n_tiles; ++gt) {
-        if (pt::tile_owner(gt, tiles_x, world) != rank) continue;
-        const uint32_t tx = gt % tiles_x, ty = gt / tiles_x;
-        for (uint32_t j = 0; j < 16u; ++j) {
-            const uint32_t y = ty * 16u + j;
-            if (y >= H) break;
-            const uint32_t x0 = tx * 16u, w = std::min(16u, W - x0);
-            memcpy(rad + ((size_t)y * W + x0) * 3, packed + ((size_t)lt * 256u + j * 16u) * 3, (size_t)w * 12);
-        }
-        ++lt;
-    }
-    return PT_OK;
+    return unpack_tiles<float>(W, H, rank, world, packed, rad);
 }
 
 }  // extern "C"

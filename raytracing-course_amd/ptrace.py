@@ -29,6 +29,8 @@ GATHER_AUTO, GATHER_RCCL, GATHER_HOST = 0, 1, 2
 # pt_stats.handoff sites, in PT_HO_* order (include/pt.h; PT_TUNE drop=<name>)
 HANDOFF_SITES = ("suspend", "flush", "ringout", "exact", "side_take", "side_yield", "side_handon", "grow_yield",
                  "grow_handon")
+# the statistics counter slots of pt_selftest_ray_intersection's counters8 (csrc/device/pt_kernels.h CTR_*)
+CTR_RAYS, CTR_NODES, CTR_PTESTS, CTR_PLANES, CTR_ERRORS, CTR_AUX, CTR_FALLBACKS, CTR_FALLBACKS_RAY = range(8)
 ABI_VERSION = 6
 # a ray query's hit record (pt_ray_hit, 24 B); a miss is id = -1 with the other fields 0
 HIT_DTYPE = np.dtype([("id", np.int32), ("t", np.float32), ("n", np.float32, (3,)), ("interior", np.uint32)])
@@ -124,6 +126,7 @@ _sig = {
     "pt_selftest_render_host": (C.c_int, [_P, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                           C.c_uint32, _P]),
     "pt_selftest_gamma_table": (C.c_int, [_P, _P]),
+    "pt_selftest_wave_plan": (C.c_int, [_P, C.POINTER(SessionOpts), C.c_uint32, C.c_char_p, C.c_size_t]),
 }
 for _name, (_res, _args) in _sig.items():
     _f = getattr(_lib, _name)
@@ -250,13 +253,23 @@ class Scene:
         ctr = np.zeros(8, np.uint64)
         _check(_lib.pt_selftest_ray_intersection(self._h, traversal, len(rays), _ptr(rays), _ptr(ids), _ptr(hits),
                                                  _ptr(ctr)))
-        return ids, hits, {"nodes": int(ctr[1]), "prim_tests": int(ctr[2]), "aux": int(ctr[5]),
-                           "fallbacks": int(ctr[6])}
+        return ids, hits, {"nodes": int(ctr[CTR_NODES]), "prim_tests": int(ctr[CTR_PTESTS]), "aux": int(ctr[CTR_AUX]),
+                           "fallbacks": int(ctr[CTR_FALLBACKS])}
 
     def selftest_render_host(self, x0, y0, w, h, spp=0, traversal=TRAVERSAL_REPLAY):
         rad = np.zeros((h, w, 3), np.float32)
         _check(_lib.pt_selftest_render_host(self._h, traversal, x0, y0, w, h, spp, _ptr(rad)))
         return rad
+
+    def wave_plan(self, cus, rank=0, world=1, traversal=TRAVERSAL_REPLAY, window=None):
+        """A session's set-up on a device of `cus` compute units, computed without one: the
+        wavefront pass's plan (a key per field; mix and mix_low tuples of four), n_slots,
+        n_tiles_local, arena_bytes and aux_stack_words."""
+        o = SessionOpts(0, rank, world, traversal, *(window or (0, 0, 0, 0)))
+        buf = C.create_string_buffer(4096)
+        _check(_lib.pt_selftest_wave_plan(self._h, C.byref(o), cus, buf, len(buf)))
+        kv = (line.split("=") for line in buf.value.decode().splitlines())
+        return {k: tuple(int(x) for x in v.split(",")) if "," in v else int(v) for k, v in kv}
 
     def gamma_table(self):
         t = np.zeros(256, np.float32)

@@ -437,3 +437,22 @@ def test_handoff_sites_mirror_the_abi():
     assert sorted(ids.values()) == list(range(n))
     assert tuple(sorted(ids, key=ids.get)) == pt.HANDOFF_SITES
     assert re.search(r"uint64_t handoff\[(\d+)\]", hdr).group(1) == str(dict(pt.Stats._fields_)["handoff"]._length_)
+
+
+def test_counter_slots_mirror_the_device_enumeration():
+    """The statistics counter slots (csrc/device/pt_kernels.h CTR_*): the whole block as the
+    device units and the host's pt_stats name it, distinct slots below the hand-off sites',
+    and ptrace's names for the slots of pt_selftest_ray_intersection's counters8."""
+    hdr = open(os.path.join(U.PKG, "csrc", "device", "pt_kernels.h")).read()
+    body = re.search(r"enum : uint32_t \{([^}]*CTR_RAYS[^}]*)\}", hdr).group(1)
+    ids = {m.group(1): int(m.group(2)) for m in re.finditer(r"\b(CTR_[A-Z_]+) = (\d+)u", body)}
+    assert ids == dict(CTR_RAYS=0, CTR_NODES=1, CTR_PTESTS=2, CTR_PLANES=3, CTR_ERRORS=4, CTR_AUX=5, CTR_FALLBACKS=6,
+                       CTR_FALLBACKS_RAY=7, CTR_COOP_RAYS=8, CTR_COOP_NODES=9, CTR_COOP_PTESTS=10, CTR_SHORT=11,
+                       CTR_HANDON=12, CTR_COOP_AUX=13, CTR_HO=16)
+    ho = ids.pop("CTR_HO")
+    assert len(set(ids.values())) == len(ids) and max(ids.values()) < ho
+    stride = int(re.search(r"#define PT_CTR_STRIDE (\d+)u", hdr).group(1))
+    assert ho + len(pt.HANDOFF_SITES) <= stride
+    mine = {k: v for k, v in vars(pt).items() if k.startswith("CTR_")}
+    assert sorted(mine.values()) == list(range(8))
+    assert mine == {k: ids[k] for k in mine}
