@@ -292,28 +292,43 @@ PT_HD T q_sel(const T (&a)[PT_QHK], uint32_t k, T dflt) {
     return v;
 }
 
+// The hit list (hidx / ht / hid / hacc) is written at ONE place in a step: the step
+// kinds (q_exec_kind) record what they want done to it in a QEdit and q_exec applies
+// it after their branches join.  An edit made inside a kind's branch makes every
+// other branch end in a copy of the whole list (24 registers) to the joined
+// registers, and the aux-node kind -- nearly every step -- paid that on every trip.
+enum : uint32_t { QE_NONE = 0u, QE_ADD = 1u, QE_REJECT = 2u };
+struct QEdit {
+    uint32_t op;                // QE_*
+    uint32_t c;                 // QE_ADD: the hitting leaf {reference index, first-min t, its
+    float t;                    //   primitive, certain-accept threshold}
+    int id;
+    float acc;
+};
+
 // A probed leaf with a primitive hit joins the list, sorted by reference index.
 // Entered hits of earlier passes lie below lb <= c, so they never move; with
 // the list full the largest entry (undecided: it is above c >= lb) or c itself
-// drops out and another pass follows.  Returns false when every slot holds an
-// entered hit (the exact DFS takes the ray).
-PT_HD bool q_add_hit(Query& q, uint32_t c, float t, int id, float acc) {
-    if (q.ne == PT_QHK) return false;
-#pragma unroll
-    for (int k = 0; k < PT_QHK; ++k) {
-        const bool sw = q.hidx[k] > c;   // empty slots hold 0xffffffff
-        const uint32_t xi = q.hidx[k];
-        const float xt = q.ht[k];
-        const int xd = q.hid[k];
-        const float xa = q.hacc[k];
-        if (sw) {
-            q.hidx[k] = c; q.ht[k] = t; q.hid[k] = id; q.hacc[k] = acc;
-            c = xi; t = xt; id = xd; acc = xa;
-        }
-    }
-    if (c != 0xffffffffu) q.overflow = 1u;   // a hitting leaf above the kept ones dropped out
+// drops out and another pass follows.  The caller has checked ne < PT_QHK (a
+// list full of entered hits: the exact DFS takes the ray).
+PT_HD void q_add_hit(Query& q, uint32_t c, float t, int id, float acc) {
+    // a hitting leaf drops out (c or the largest entry) iff the list was full
+    if (q.hidx[PT_QHK - 1] != 0xffffffffu) q.overflow = 1u;
     else q.nh = q.nh + 1u;
-    return true;
+    // The list is sorted and c is not in it, so the slots above c are its tail: from the
+    // top down each takes its lower neighbour's entry and the lowest of them takes c.
+    // Selects, no branch per slot and no entry carried from slot to slot; the listed
+    // entries come out as a slot-by-slot exchange leaves them (empty slots: any t / prim)
+#pragma unroll
+    for (int k = PT_QHK - 1; k >= 0; --k) {
+        const int l = k > 0 ? k - 1 : 0;
+        const bool up = q.hidx[k] > c;             // empty slots hold 0xffffffff
+        const bool upl = k > 0 && q.hidx[l] > c;   // ... and so does the slot below it
+        q.ht[k] = up ? (upl ? q.ht[l] : t) : q.ht[k];
+        q.hid[k] = up ? (upl ? q.hid[l] : id) : q.hid[k];
+        q.hacc[k] = up ? (upl ? q.hacc[l] : acc) : q.hacc[k];
+        q.hidx[k] = up ? (upl ? q.hidx[l] : c) : q.hidx[k];
+    }
 }
 
 // every hitting leaf of the pass is decided: another pass above lb, or done
@@ -375,9 +390,14 @@ PT_HD void q_decide(Query& q) {
     q_pass_done(q);
 }
 
-// hitting leaf hidx[ne] is not entered: it leaves the list (an unentered leaf
-// changes neither the result nor any bound)
-PT_HD void q_rejected(Query& q) {
+// hitting leaf hidx[ne] (= cand) is not entered (an unentered leaf changes neither the
+// result nor any bound): the kind's part, and the list's (QE_REJECT: it leaves the list)
+PT_HD void q_rejected(Query& q, QEdit& ed) {
+    ed.op = QE_REJECT;
+    q.lb = q.cand + 1u;
+    q_next_decision(q);
+}
+PT_HD void q_drop_rejected(Query& q) {
 #pragma unroll
     for (int k = 0; k + 1 < PT_QHK; ++k) {
         if ((uint32_t)k >= q.ne) {
@@ -389,8 +409,6 @@ PT_HD void q_rejected(Query& q) {
     }
     q.hidx[PT_QHK - 1] = 0xffffffffu;
     q.nh = q.nh - 1u;
-    q.lb = q.cand + 1u;
-    q_next_decision(q);
 }
 
 // min of the recorded hits strictly inside (a, r) (the left subtree of a when
@@ -565,7 +583,10 @@ PT_HD void q_exec_aux(const SceneView& S, Query& q, QCounts& C, Mem& stk, const 
         float tn, tf, un, uf;
         aux_slab16(f2u(ea.x), f2u(ea.y), f2u(ea.z), q.inv, oinv, tn, tf);
         aux_slab16(f2u(ea.w), f2u(eb.x), f2u(eb.y), q.inv, oinv, un, uf);
-        hit[k] = tn <= tf && tf >= 0.f && (mwide || (un - mt <= uf + mt && uf + mt >= 0.f));
+        // own box AND (margin infinite OR widened hit region): plain & and |, so the four
+        // compares meet as lane masks and none becomes a 0/1 register.  With the margin
+        // infinite the region's compares may see inf - inf = NaN: false, and not asked
+        hit[k] = (tn <= tf) & (tf >= 0.f) & (mwide | ((un - mt <= uf + mt) & (uf + mt >= 0.f)));
     }
     if (pt_any(q.par != 0u)) {
 #pragma unroll
@@ -598,9 +619,13 @@ PT_HD void q_exec_aux(const SceneView& S, Query& q, QCounts& C, Mem& stk, const 
         // a subtree is skipped when all its leaves lie below lb (decided in an
         // earlier pass), or above the largest listed hitting leaf of a full
         // list: it could only add hits the list would drop, so another pass follows
-        const bool above = isleaf ? lidx > hmax
-                                  : (hmax != 0xffffffffu && ((rng & 0xffffu) << S.aux_rshift) > hmax);
-        const bool fresh = isleaf ? lidx >= q.lb : ((rng >> 16) << S.aux_rshift) >= q.lb;
+        // (the entry's leaf range [rlo, rhi]: a leaf's own index, an internal entry's two
+        // ends; selects, not branches.  With the list not full hmax is 0xffffffff and
+        // nothing lies above it)
+        const uint32_t rlo = isleaf ? lidx : (rng & 0xffffu) << S.aux_rshift;
+        const uint32_t rhi = isleaf ? lidx : (rng >> 16) << S.aux_rshift;
+        const bool above = rlo > hmax;
+        const bool fresh = rhi >= q.lb;
         ovf = ovf || (h && fresh && above);
         const bool take = h && fresh && !above;
         const uint32_t item = isleaf ? (PT_LEAFQ | rng) : code;
@@ -623,8 +648,9 @@ PT_HD void q_exec_aux(const SceneView& S, Query& q, QCounts& C, Mem& stk, const 
     q_aux_next(q, stk, next);
 }
 
+// One step kind's transition.  It reads the hit list and never writes it: `ed` takes the edit.
 template <class Mem>
-PT_HD void q_exec_kind(const SceneView& S, Query& q, QCounts& C, Mem& stk, const F4 r[8] QP_ARG) {
+PT_HD void q_exec_kind(const SceneView& S, Query& q, QCounts& C, Mem& stk, const F4 r[8], QEdit& ed QP_ARG) {
     if (q.phase == Q_AUX && !(q.node & PT_LEAFQ)) {
         QP_STAMP(0);
         q_exec_aux(S, q, C, stk, r);
@@ -708,11 +734,14 @@ PT_HD void q_exec_kind(const SceneView& S, Query& q, QCounts& C, Mem& stk, const
         q.li = li + 1u;
         if (q.li < q.lcnt) return;
         q.li = 0u;
-        if (q.lid >= 0 && !q_add_hit(q, q.cand, q.lt, q.lid, q.lacc)) {
-            q.phase = Q_EXACT;
-            return;
+        if (q.lid >= 0) {
+            if (q.ne == PT_QHK) {
+                q.phase = Q_EXACT;   // every slot holds an entered hit
+                return;
+            }
+            ed = QEdit{QE_ADD, q.cand, q.lt, q.lid, q.lacc};
         }
-        q_aux_next(q, stk, 0xffffffffu);
+        q_aux_next(q, stk, 0xffffffffu);   // (does not read the list)
         return;
     }
     // Q_REPLAY: is hitting leaf hidx[ne] (= cand) entered?
@@ -734,7 +763,7 @@ PT_HD void q_exec_kind(const SceneView& S, Query& q, QCounts& C, Mem& stk, const
             return;
         }
         if (v == 0u) {
-            q_rejected(q);
+            q_rejected(q, ed);
             return;
         }
         // undecided: test the root path below a* = LCA(last recorded hit, cand).
@@ -797,7 +826,7 @@ PT_HD void q_exec_kind(const SceneView& S, Query& q, QCounts& C, Mem& stk, const
         if (!node_enter(nd, q.ray, q.inv, q.bound, q.par != 0u)) reject = true;
     }
     if (reject) {
-        q_rejected(q);
+        q_rejected(q, ed);
         return;
     }
     q.pos += 4u;
@@ -805,14 +834,22 @@ PT_HD void q_exec_kind(const SceneView& S, Query& q, QCounts& C, Mem& stk, const
     else q.walk = R_WALK_E;
 }
 
-// one step's compute: the step kind's transition, then the precomputed accepts
+// one step's compute: the step kind's transition, its edit of the hit list (each kind of
+// edit only when a lane of the wave has one), then the precomputed accepts
 template <class Mem>
 PT_HD void q_exec(const SceneView& S, Query& q, QCounts& C, Mem& stk, const F4 r[8] QP_ARG) {
+    QEdit ed{QE_NONE, 0u, 0.f, 0, 0.f};
 #ifdef PT_QPROF_DEV
-    q_exec_kind(S, q, C, stk, r, qp);
+    q_exec_kind(S, q, C, stk, r, ed, qp);
 #else
-    q_exec_kind(S, q, C, stk, r);
+    q_exec_kind(S, q, C, stk, r, ed);
 #endif
+    if (pt_any(ed.op == QE_ADD)) {
+        if (ed.op == QE_ADD) q_add_hit(q, ed.c, ed.t, ed.id, ed.acc);
+    }
+    if (pt_any(ed.op == QE_REJECT)) {
+        if (ed.op == QE_REJECT) q_drop_rejected(q);
+    }
     if (q.phase == Q_DECIDE) q_decide(q);
 }
 
