@@ -676,8 +676,17 @@ float pdf_mix(const Scene& S, V3 x, V3 n, V3 d) {                  // :401-416
 
 inline V3 reflect(V3 n, V3 dir) { return dir - (2.0f * n) * fdot(n, dir); }  // src/scene.cpp:79-81
 
+// Vertex census (the restatement's own, nothing of the reference's): per primitive id, how
+// many path vertices took each branch of the material switch below, on either side of the
+// surface.  A cell is census[id * CEN_CELLS + 2 * event + interior].
+enum CenEvent : uint32_t { CEN_DIFFUSE = 0, CEN_METALLIC = 1, CEN_TIR = 2, CEN_FRESNEL = 3, CEN_REFRACT = 4 };
+constexpr uint32_t CEN_CELLS = 10;
+inline void tally(uint64_t* cen, int id, CenEvent e, bool interior) {
+    if (cen) ++cen[(size_t)id * CEN_CELLS + 2 * e + (interior ? 1 : 0)];
+}
+
 // src/scene.cpp:83-178 (recursive, like the reference)
-V3 ray_trace(const Scene& S, Rng& R, const Ray& ray, unsigned depth, uint64_t* loc) {
+V3 ray_trace(const Scene& S, Rng& R, const Ray& ray, unsigned depth, uint64_t* loc, uint64_t* cen) {
     if (depth == 0) return V3{0.f, 0.f, 0.f};
     ++loc[0];
     const RHit rh = ray_intersection(S, ray, loc);
@@ -691,17 +700,19 @@ V3 ray_trace(const Scene& S, Rng& R, const Ray& ray, unsigned depth, uint64_t* l
     V3 other{0.f, 0.f, 0.f};
     switch (pr.mat) {
         case M_DIFFUSE: {
+            tally(cen, rh.id, CEN_DIFFUSE, interior);
             const V3 p_outer = p + eps * normal;
             const V3 dir = sample_mix(S, R, p_outer, normal);
             if (fdot(dir, normal) <= 0) break;
             const float pw = pdf_mix(S, p_outer, normal, dir);
-            const V3 L = ray_trace(S, R, Ray{p + eps * dir, dir}, depth - 1, loc);
+            const V3 L = ray_trace(S, R, Ray{p + eps * dir, dir}, depth - 1, loc, cen);
             other = (pr.col / kPI) * L * fdot(dir, normal) * (1 / pw);
             break;
         }
         case M_METALLIC: {
+            tally(cen, rh.id, CEN_METALLIC, interior);
             const V3 rd = reflect(normal, fnormalize(ray.d));
-            const V3 L = ray_trace(S, R, Ray{p + eps * rd, rd}, depth - 1, loc);
+            const V3 L = ray_trace(S, R, Ray{p + eps * rd, rd}, depth - 1, loc, cen);
             other = pr.col * L;
             break;
         }
@@ -712,20 +723,23 @@ V3 ray_trace(const Scene& S, Rng& R, const Ray& ray, unsigned depth, uint64_t* l
             const float cosn = fdot(normal, dir);
             const float sin2 = (float)((double)(eta1 / eta2) * std::sqrt((double)smax(0.f, 1 - cosn * cosn)));
             if (std::fabs((double)sin2) > 1.) {
+                tally(cen, rh.id, CEN_TIR, interior);
                 const V3 rd = reflect(normal, fnormalize(ray.d));
-                other = ray_trace(S, R, Ray{p + eps * rd, rd}, depth - 1, loc);
+                other = ray_trace(S, R, Ray{p + eps * rd, rd}, depth - 1, loc, cen);
                 break;
             }
             const float r0 = (float)std::pow((double)((eta1 - eta2) / (eta1 + eta2)), 2.);
             const float rr = (float)((double)r0 + (double)(1 - r0) * std::pow((double)(1 - cosn), 5.));
             if (R.uniform() < rr) {
+                tally(cen, rh.id, CEN_FRESNEL, interior);
                 const V3 rd = reflect(normal, fnormalize(ray.d));
-                other = ray_trace(S, R, Ray{p + eps * rd, rd}, depth - 1, loc);
+                other = ray_trace(S, R, Ray{p + eps * rd, rd}, depth - 1, loc, cen);
                 break;
             }
+            tally(cen, rh.id, CEN_REFRACT, interior);
             const float cos2 = (float)std::sqrt((double)(1 - sin2 * sin2));
             const V3 rd = (eta1 / eta2) * (-1.f * dir) + (eta1 / eta2 * cosn - cos2) * normal;
-            V3 L = ray_trace(S, R, Ray{p + eps * rd, rd}, depth - 1, loc);
+            V3 L = ray_trace(S, R, Ray{p + eps * rd, rd}, depth - 1, loc, cen);
             if (!interior) L = pr.col * L;
             other = L;
             break;
@@ -749,12 +763,13 @@ Ray get_to_ray(const Scene& S, const Cam& c, float x, float y) {  // src/scene.c
 }
 
 // src/scene.cpp:189-203
-V3 sample_pixel(const Scene& S, const Cam& c, Rng& R, unsigned x, unsigned y, unsigned spp, uint64_t* loc) {
+V3 sample_pixel(const Scene& S, const Cam& c, Rng& R, unsigned x, unsigned y, unsigned spp, uint64_t* loc,
+                uint64_t* cen) {
     V3 sum{0.f, 0.f, 0.f};
     for (unsigned i = 0; i < spp; ++i) {
         const float fx = (float)x + R.uniform();
         const float fy = (float)y + R.uniform();
-        sum = sum + ray_trace(S, R, get_to_ray(S, c, fx, fy), S.ray_depth, loc);
+        sum = sum + ray_trace(S, R, get_to_ray(S, c, fx, fy), S.ray_depth, loc, cen);
     }
     return (1.f / (float)spp) * sum;
 }
@@ -832,6 +847,15 @@ int oracle_dump_bvh(const oracle_scene* o, void* nodes_out, void* prims_out) {
 // counters[4] (may be NULL): rays, node visits, leaf primitive tests, plane tests.
 int oracle_render(oracle_scene* o, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t spp,
                   int nthreads, uint8_t* rgb, float* rad, uint64_t* counters) {
+    return oracle_render_census(o, x0, y0, w, h, spp, nthreads, rgb, rad, counters, nullptr);
+}
+
+// The same render, and the vertex census: census[n_prims * 10] u64 (may be NULL), per primitive
+// id (post-InitScene order) {diffuse, metallic, total internal reflection, Fresnel reflection,
+// refraction} x {outside, interior}.  Each thread counts into its own table; the tables are
+// summed after the join, so the counts do not depend on the thread count.
+int oracle_render_census(oracle_scene* o, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t spp,
+                         int nthreads, uint8_t* rgb, float* rad, uint64_t* counters, uint64_t* census) {
     const Scene& S = o->s;
     if (spp == 0) spp = S.samples;
     const Cam cam = camera_tans(S);
@@ -840,8 +864,11 @@ int oracle_render(oracle_scene* o, uint32_t x0, uint32_t y0, uint32_t w, uint32_
     std::atomic<uint64_t> c_rays{0}, c_nodes{0}, c_pt{0}, c_pl{0};
     if (nthreads <= 0) nthreads = (int)std::thread::hardware_concurrency();
     if (nthreads <= 0) nthreads = 1;
-    auto worker = [&]() {
+    const size_t n_cen = census ? S.prims.size() * CEN_CELLS : 0;
+    std::vector<std::vector<uint64_t>> cens((size_t)nthreads, std::vector<uint64_t>(n_cen, 0));
+    auto worker = [&](int tid) {
         uint64_t loc[4] = {0, 0, 0, 0};
+        uint64_t* cen = census ? cens[(size_t)tid].data() : nullptr;
         for (;;) {
             const uint64_t k0 = next.fetch_add(64);
             if (k0 >= total) break;
@@ -849,7 +876,7 @@ int oracle_render(oracle_scene* o, uint32_t x0, uint32_t y0, uint32_t w, uint32_
             for (uint64_t k = k0; k < k1; ++k) {
                 const uint32_t x = x0 + (uint32_t)(k % w), y = y0 + (uint32_t)(k / w);
                 Rng R(y * S.W + x);  // src/scene.cpp:216: minstd_rand rnd(i), i = y*W + x
-                const V3 c = sample_pixel(S, cam, R, x, y, spp, loc);
+                const V3 c = sample_pixel(S, cam, R, x, y, spp, loc, cen);
                 if (rad) { rad[k * 3] = c.x; rad[k * 3 + 1] = c.y; rad[k * 3 + 2] = c.z; }
                 if (rgb) tonemap(c, rgb + k * 3);
             }
@@ -857,10 +884,29 @@ int oracle_render(oracle_scene* o, uint32_t x0, uint32_t y0, uint32_t w, uint32_
         c_rays += loc[0]; c_nodes += loc[1]; c_pt += loc[2]; c_pl += loc[3];
     };
     std::vector<std::thread> th;
-    for (int i = 1; i < nthreads; ++i) th.emplace_back(worker);
-    worker();
+    for (int i = 1; i < nthreads; ++i) th.emplace_back(worker, i);
+    worker(0);
     for (auto& t : th) t.join();
+    for (size_t k = 0; k < n_cen; ++k) {
+        census[k] = 0;
+        for (const auto& c : cens) census[k] += c[k];
+    }
     if (counters) { counters[0] = c_rays; counters[1] = c_nodes; counters[2] = c_pt; counters[3] = c_pl; }
+    return 0;
+}
+
+// Per primitive id (post-InitScene order) 6 u32: type, material, IOR's f32 bits, emission > 0,
+// POSITION != 0, ROTATION != identity -- what the census's readers need to name a cell's kind.
+int oracle_prim_info(const oracle_scene* o, uint32_t* out) {
+    for (const Prim& p : o->s.prims) {
+        uint32_t ior;
+        std::memcpy(&ior, &p.ior, 4);
+        out[0] = p.type; out[1] = p.mat; out[2] = ior;
+        out[3] = (p.emission.x > 0 || p.emission.y > 0 || p.emission.z > 0) ? 1u : 0u;
+        out[4] = (p.pos.x != 0.f || p.pos.y != 0.f || p.pos.z != 0.f) ? 1u : 0u;
+        out[5] = (p.rot.x != 0.f || p.rot.y != 0.f || p.rot.z != 0.f || p.rot.w != 1.f) ? 1u : 0u;
+        out += 6;
+    }
     return 0;
 }
 

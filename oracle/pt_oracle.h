@@ -14,6 +14,12 @@ int oracle_info(const oracle_scene* o, uint32_t* out8);
 int oracle_dump_bvh(const oracle_scene* o, void* nodes_out, void* prims_out);
 int oracle_render(oracle_scene* o, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t spp,
                   int nthreads, uint8_t* rgb, float* rad, uint64_t* counters);
+/* oracle_render + the vertex census: census[n_prims * 10] u64, per primitive id {diffuse,
+ * metallic, total internal reflection, Fresnel reflection, refraction} x {outside, interior} */
+int oracle_render_census(oracle_scene* o, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t spp,
+                         int nthreads, uint8_t* rgb, float* rad, uint64_t* counters, uint64_t* census);
+/* per primitive id 6 u32: type, material, IOR bits, emissive, moved, rotated */
+int oracle_prim_info(const oracle_scene* o, uint32_t* out);
 int oracle_ray_intersection(const oracle_scene* o, uint32_t n, const float* rays, int32_t* ids, float* hit);
 int oracle_rng(uint32_t seed, uint32_t n, float* out);
 void oracle_tonemap(uint32_t n, const float* rad, uint8_t* rgb);

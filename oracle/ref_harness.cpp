@@ -26,6 +26,9 @@
 //   trav   <scene> <nrays> <seed> <out.bin>
 //          random rays -> reference Scene::RayIntersection (scene.cpp:46-77)
 //          and BVH_t::Intersect with INF bound (bvh.cpp:181-225).
+//   rays   <scene> <rays.f32> <out.bin>
+//          the caller's rays (n x 6 f32: origin, direction, used as they are) through the
+//          same two calls; the record per ray is trav's.
 // Standard and glm headers first, so that only the reference's own classes
 // see the access override below.
 #include <algorithm>
@@ -174,6 +177,22 @@ static int mode_rng(int argc, char** argv) {
     return 0;
 }
 
+// one 72-byte record: the ray, then RayIntersection's and BVH_t::Intersect's answers
+static void put_trav_record(std::ofstream& o, Scene& s, const Ray& r) {
+    ray_intersection_t a = s.RayIntersection(r);
+    ray_intersection_t b = s.scene_bvh.Intersect(s.primitives, r, INF);
+    put_f32(o, r.o.x); put_f32(o, r.o.y); put_f32(o, r.o.z);
+    put_f32(o, r.d.x); put_f32(o, r.d.y); put_f32(o, r.d.z);
+    for (const ray_intersection_t* q : {&a, &b}) {
+        put_i32(o, q->id);
+        const bool h = q->id != -1;
+        put_f32(o, h ? q->isec.t : 0.f);
+        put_f32(o, h ? q->isec.normal.x : 0.f); put_f32(o, h ? q->isec.normal.y : 0.f);
+        put_f32(o, h ? q->isec.normal.z : 0.f);
+        put_u32(o, h ? (uint32_t)q->isec.interior : 0u);
+    }
+}
+
 static int mode_trav(int argc, char** argv) {
     if (argc < 6) return 2;
     Scene s;
@@ -203,30 +222,33 @@ static int mode_trav(int argc, char** argv) {
             if (k % 11 == 4) d.y = -0.f;
             r = Ray(p, glm::normalize(d));
         }
-        ray_intersection_t a = s.RayIntersection(r);
-        ray_intersection_t b = s.scene_bvh.Intersect(s.primitives, r, INF);
-        put_f32(o, r.o.x); put_f32(o, r.o.y); put_f32(o, r.o.z);
-        put_f32(o, r.d.x); put_f32(o, r.d.y); put_f32(o, r.d.z);
-        for (const ray_intersection_t* q : {&a, &b}) {
-            put_i32(o, q->id);
-            const bool h = q->id != -1;
-            put_f32(o, h ? q->isec.t : 0.f);
-            put_f32(o, h ? q->isec.normal.x : 0.f); put_f32(o, h ? q->isec.normal.y : 0.f);
-            put_f32(o, h ? q->isec.normal.z : 0.f);
-            put_u32(o, h ? (uint32_t)q->isec.interior : 0u);
-        }
+        put_trav_record(o, s, r);
     }
     return 0;
 }
 
+static int mode_rays(int argc, char** argv) {
+    if (argc < 5) return 2;
+    Scene s;
+    load(s, argv[2]);
+    std::ifstream in(argv[3], std::ios::binary);
+    if (!in) { std::fprintf(stderr, "cannot open %s\n", argv[3]); return 1; }
+    std::ofstream o(argv[4], std::ios::binary);
+    float f[6];
+    while (in.read(reinterpret_cast<char*>(f), sizeof f))
+        put_trav_record(o, s, Ray(glm::vec3{f[0], f[1], f[2]}, glm::vec3{f[3], f[4], f[5]}));
+    return 0;
+}
+
 int main(int argc, char** argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: ref_harness bvh|render|rng|trav ...\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: ref_harness bvh|render|rng|trav|rays ...\n"); return 2; }
     const std::string m = argv[1];
     int rc = 2;
     if (m == "bvh") rc = mode_bvh(argc, argv);
     else if (m == "render") rc = mode_render(argc, argv);
     else if (m == "rng") rc = mode_rng(argc, argv);
     else if (m == "trav") rc = mode_trav(argc, argv);
+    else if (m == "rays") rc = mode_rays(argc, argv);
     if (rc == 2) std::fprintf(stderr, "bad arguments for mode %s\n", m.c_str());
     return rc;
 }

@@ -20,6 +20,8 @@ GEN = os.path.join(SCENES, "gen")
 PKG = os.path.join(REPO, "raytracing-course_amd")
 sys.path.insert(0, SCENES)
 import make_scene  # noqa: E402
+sys.path.insert(0, os.path.join(REPO, "tests"))
+import _material_scenes  # noqa: E402
 
 _lock = threading.Lock()
 _cache = {}
@@ -45,6 +47,8 @@ def oracle():
         lib.oracle_info.argtypes = [P, P]
         lib.oracle_dump_bvh.argtypes = [P, P, P]
         lib.oracle_render.argtypes = [P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, P, P, P]
+        lib.oracle_render_census.argtypes = lib.oracle_render.argtypes + [P]
+        lib.oracle_prim_info.argtypes = [P, P]
         lib.oracle_ray_intersection.argtypes = [P, C.c_uint32, P, P, P]
         lib.oracle_rng.argtypes = [C.c_uint32, C.c_uint32, P]
         lib.oracle_tonemap.argtypes = [C.c_uint32, P, P]
@@ -69,6 +73,11 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+CENSUS_EVENTS = ("diffuse", "metallic", "tir", "fresnel", "refract")
+PRIM_TYPES = {1: "plane", 2: "box", 4: "ellipsoid", 8: "triangle"}
+MATERIALS = {0: "diffuse", 1: "metallic", 2: "dielectric"}
+
+
 class OracleScene:
     def __init__(self, path):
         self.lib = oracle()
@@ -84,14 +93,30 @@ class OracleScene:
             self.lib.oracle_free(self.h)
             self.h = None
 
-    def render(self, x0=0, y0=0, w=None, h=None, spp=0, threads=0):
+    def render(self, x0=0, y0=0, w=None, h=None, spp=0, threads=0, census=False):
+        """(image, radiance, counters); with census=True the counters also hold "census": the
+        vertex events per primitive id, shape (n_prims, len(CENSUS_EVENTS), 2 = outside/interior)"""
         w = self.W if w is None else w
         h = self.H if h is None else h
         rgb = np.zeros((h, w, 3), np.uint8)
         rad = np.zeros((h, w, 3), np.float32)
         ctr = np.zeros(4, np.uint64)
-        self.lib.oracle_render(self.h, x0, y0, w, h, spp, threads, _p(rgb), _p(rad), _p(ctr))
-        return rgb, rad, {"rays": int(ctr[0]), "nodes": int(ctr[1]), "prim_tests": int(ctr[2]), "planes": int(ctr[3])}
+        cen = np.zeros((self.n_prims, len(CENSUS_EVENTS), 2), np.uint64) if census else None
+        if census:
+            self.lib.oracle_render_census(self.h, x0, y0, w, h, spp, threads, _p(rgb), _p(rad), _p(ctr), _p(cen))
+        else:
+            self.lib.oracle_render(self.h, x0, y0, w, h, spp, threads, _p(rgb), _p(rad), _p(ctr))
+        out = {"rays": int(ctr[0]), "nodes": int(ctr[1]), "prim_tests": int(ctr[2]), "planes": int(ctr[3])}
+        if census:
+            out["census"] = cen.astype(np.int64)
+        return rgb, rad, out
+
+    def prim_info(self):
+        """per primitive id: type (PRIM_TYPES), material (MATERIALS), ior, emissive, moved, rotated"""
+        raw = np.zeros((self.n_prims, 6), np.uint32)
+        self.lib.oracle_prim_info(self.h, _p(raw))
+        return [{"type": PRIM_TYPES[int(r[0])], "material": MATERIALS[int(r[1])], "ior": float(r[2:3].view(np.float32)[0]),
+                 "emissive": bool(r[3]), "moved": bool(r[4]), "rotated": bool(r[5])} for r in raw]
 
     def dump_bvh(self):
         nb = np.zeros(self.n_nodes * 40, np.uint8)
@@ -149,6 +174,15 @@ def golden_image(name):
 def scene_path(src, gen=None):
     """Path of a scene file: a committed scene, a pinned config, or a generated variant."""
     os.makedirs(GEN, exist_ok=True)
+    if gen is None and src.startswith(_material_scenes.PREFIX):
+        text = _material_scenes.scene_text(src[len(_material_scenes.PREFIX):])
+        out = os.path.join(GEN, "%s_%s.txt" % (src.replace(":", "_"), md5(text.encode())[:8]))
+        with _lock:
+            if not os.path.exists(out):
+                with open(out + ".tmp", "w") as f:
+                    f.write(text)
+                os.replace(out + ".tmp", out)
+        return out
     if gen is None and src in make_scene.CONFIGS:
         out = os.path.join(GEN, src + ".txt")
         with _lock:

@@ -14,6 +14,10 @@ Outputs (all little-endian):
   rng_<seed>.f32                 3*N floats: N uniform, N normal, N mixed draws
   trav_<scene>.bin               per ray: o,d (6 f32) + 2 x (id i32, t, n.xyz f32,
                                  interior u32) for RayIntersection / BVH_t::Intersect
+
+  --images NAME...   add / refresh the named image fixtures in the existing manifest
+  --rays NAME...     add / refresh the named ray fixtures (RAYS: our own rays through the
+                     reference's two intersection calls) in the existing manifest
 """
 import hashlib
 import json
@@ -26,13 +30,19 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(REPO, "scenes"))
 import make_scene  # noqa: E402
+sys.path.insert(0, os.path.join(REPO, "tests"))
+import _material_scenes  # noqa: E402
 
 REF = os.path.join(REPO, "oracle", "_ref")
 SCENES = os.path.join(REPO, "scenes")
 
 # name -> (scene source, generator args or None, window or None)
 #   generator args: (W, H, S, subdivide, variant)
+#   a scene source "material:<name>" is tests/_material_scenes.py's text of that name
 IMAGES = {
+    "mat_matrix_24x24x8": ("material:matrix", None, None),
+    "mat_inside_24x24x8": ("material:inside", None, None),
+    "mat_camera_23x17x8": ("material:camera", None, None),
     "p51_64x48x16": ("practice5_1.txt", (64, 48, 16, False, "diffuse"), None),
     "p52_64x48x16": ("practice5_2.txt", (64, 48, 16, False, "diffuse"), None),
     "dragon_64x64x16": ("practice5_dragon_10k.txt", (64, 64, 16, False, "diffuse"), None),
@@ -92,6 +102,8 @@ RNG_N = 2048
 
 TRAV = {"dragon10k": ("practice5_dragon_10k.txt", None), "standin": ("c3", None)}
 TRAV_RAYS = 4096
+# name -> (scene source, the rays' generator): trav_<name>.bin from ref_harness rays
+RAYS = {"edges": ("material:edges", _material_scenes.edge_rays)}
 
 # full-resolution reference md5s measured in the survey container;
 # config 1 is re-measured here, config 2 (320 s) is carried over.
@@ -107,6 +119,11 @@ def md5f(path):
 
 def scene_file(tmp, src, gen):
     """Return a path to the scene text for fixture generation."""
+    if src.startswith(_material_scenes.PREFIX):
+        out = os.path.join(tmp, src.replace(":", "_") + ".txt")
+        with open(out, "w") as f:
+            f.write(_material_scenes.scene_text(src[len(_material_scenes.PREFIX):]))
+        return out
     if src in make_scene.CONFIGS and gen is None:
         out = os.path.join(tmp, src + ".txt")
         if not os.path.exists(out):
@@ -136,6 +153,8 @@ def render_image(harness, tmp, name, table=None):
     subprocess.check_call(cmd)
     entry = {"scene": src, "gen": list(gen) if gen else None, "window": list(win) if win else None,
              "ppm_md5": md5f(ppm), "rad_md5": md5f(rad)}
+    if src.startswith(_material_scenes.PREFIX):
+        entry["scene_md5"] = md5f(sc)   # the scene text this fixture was recorded from
     if not win:
         # the windowless harness render must equal the real CLI byte-for-byte
         cli_ppm = os.path.join(tmp, name + "_cli.ppm")
@@ -143,6 +162,21 @@ def render_image(harness, tmp, name, table=None):
         assert md5f(cli_ppm) == entry["ppm_md5"], name
     print("image", name, entry["ppm_md5"])
     return entry
+
+
+def record_rays(harness, tmp, name):
+    """A RAYS fixture: our rays, the reference's answers, in trav's record."""
+    src, gen_rays = RAYS[name]
+    sc = scene_file(tmp, src, None)
+    rays = gen_rays()
+    assert rays.shape == (TRAV_RAYS, 6) and rays.dtype == "float32"
+    rf = os.path.join(tmp, name + "_rays.f32")
+    rays.tofile(rf)
+    p = os.path.join(HERE, "trav_%s.bin" % name)
+    subprocess.check_call([harness, "rays", sc, rf, p])
+    assert os.path.getsize(p) == TRAV_RAYS * 72
+    print("rays", name, md5f(p))
+    return {"scene": src, "rays": TRAV_RAYS, "md5": md5f(p), "scene_md5": md5f(sc), "rays_md5": md5f(rf)}
 
 
 def render_deep(harness, tmp, name):
@@ -192,6 +226,15 @@ def main():
         with open(os.path.join(HERE, "manifest.json"), "w") as f:
             json.dump(manifest, f, indent=1, sort_keys=True)
         return 0
+    if len(sys.argv) > 2 and sys.argv[1] == "--rays":
+        with open(os.path.join(HERE, "manifest.json")) as f:
+            manifest = json.load(f)
+        with tempfile.TemporaryDirectory() as tmp:
+            for name in sys.argv[2:]:
+                manifest["trav"][name] = record_rays(harness, tmp, name)
+        with open(os.path.join(HERE, "manifest.json"), "w") as f:
+            json.dump(manifest, f, indent=1, sort_keys=True)
+        return 0
     manifest = {"images": {}, "rng": {}, "trav": {}, "bvh": {}, "full": {},
                 "generator": "tests/golden/make_golden.py", "reference": "FeggieBoss/raytracing-course hw5"}
     with tempfile.TemporaryDirectory() as tmp:
@@ -206,6 +249,8 @@ def main():
             p = os.path.join(HERE, "trav_%s.bin" % name)
             subprocess.check_call([harness, "trav", sc, str(TRAV_RAYS), "20241015", p])
             manifest["trav"][name] = {"scene": src, "rays": TRAV_RAYS, "md5": md5f(p)}
+        for name in RAYS:
+            manifest["trav"][name] = record_rays(harness, tmp, name)
         for name, src in [("practice5_1", "practice5_1.txt"), ("practice5_2", "practice5_2.txt"),
                           ("dragon10k", "practice5_dragon_10k.txt"), ("standin", "c3")]:
             sc = scene_file(tmp, src, None) if src in make_scene.CONFIGS else os.path.join(SCENES, src)

@@ -200,8 +200,9 @@ def test_traversal_matches_reference_kat(name, trav):
 
 
 HOST_RENDER = ["p51_64x48x16", "p52_64x48x16", "dragon_metal_64x64x8", "dragon_glass_64x64x8",
-               "hw3s2_48x48x8", "hw3s3_48x48x8", "hw3s4_48x48x8", "hw3s5_48x48x8", "rabbid_48x48x4",
-               "c2_win_240_200_24x24"]
+               "hw3s2_48x48x8", "hw3s3_48x48x8",
+               "mat_matrix_24x24x8", "mat_inside_24x24x8", "mat_camera_23x17x8",   # _material_scenes.py
+               "hw3s4_48x48x8", "hw3s5_48x48x8", "rabbid_48x48x4", "c2_win_240_200_24x24"]
 
 
 @pytest.mark.parametrize("trav", sorted(TRAVERSALS))
@@ -241,7 +242,7 @@ def test_coop_query_matches_reference_kat(name, monkeypatch):
     assert rctr["nodes"] <= ctr["nodes"]
 
 
-@pytest.mark.parametrize("name", HOST_RENDER[:6])
+@pytest.mark.parametrize("name", HOST_RENDER[:9])
 def test_coop_integrator_on_host_bit_exact(name, monkeypatch):
     monkeypatch.setenv("PT_TUNE", "qengine=coop")
     m, img, rad = U.golden_image(name)
