@@ -31,6 +31,10 @@
 //
 // qc_run() is the same algorithm on one thread (host tests, PT_TUNE
 // qengine=coop in the self-tests); qc_team() / qc_pool() in pt_wcoop.hip are the wave forms.
+// Its rules are pt_trace.h's: step 2 is leaf_first_min, step 3's bound is
+// bound_between and its node test node_enter (the wave forms keep a ballot loop
+// over compact records, qc_leaf_test, and a cross-lane scan, qc_decide).
+// Stated here: qc_slab_hit, the bound-free filtered slab test of step 2.
 #pragma once
 #include "pt_query.h"
 
@@ -58,37 +62,19 @@ PT_HD bool qc_slab_hit(const Node& nd, const Ray& ray, f3 rinv, bool exact) {
     return node_slab(nd, ray, t, in);
 }
 
-// the bound the recursion carries at node v of a root path (v's parent `prev`,
-// bound there `b`): a right child's bound is the minimum over the entered hits
-// strictly inside (prev, v) -- its left sibling's subtree -- if there is one.
-// `rec_idx/rec_t` = the entered hits so far, in preorder.
-template <class Rec>
-PT_HD float qc_child_bound(const Rec& rec, uint32_t nrec, uint32_t prev, uint32_t v, float b) {
-    if (v == prev + 1u) return b;   // left child: the parent's bound
-    float m = b;
-    bool any = false;
-    for (uint32_t r = 0; r < nrec; ++r) {
-        const uint32_t i = rec.idx(r);
-        if (i > prev && i < v) {
-            const float t = rec.t(r);
-            if (!any || t < m) m = t;
-            any = true;
-        }
-    }
-    return m;
-}
-
-// is hitting leaf c entered? (its whole root path passes with the carried bounds)
-template <class Rec>
+// is hitting leaf c entered? (its whole root path passes with the carried bounds:
+// a left child -- parent + 1 -- keeps its parent's bound, a right child takes
+// bound_between over the entered hits so far, rec_idx / rec_t, in preorder)
+template <int N>
 PT_HD bool qc_path_entered(const SceneView& S, const Ray& ray, f3 inv, bool par, float P, uint32_t c,
-                           const Rec& rec, uint32_t nrec, QCounts& C) {
+                           const uint32_t (&rec_idx)[N], const float (&rec_t)[N], uint32_t nrec, QCounts& C) {
     const uint32_t info = S.anc_info[c];
     const uint32_t off = info & 0x03ffffffu, len = info >> 26;
     float b = P;
     uint32_t prev = 0u;
     for (uint32_t j = 0; j < len; ++j) {
         const uint32_t v = S.anc[off + j];
-        if (j > 0u) b = qc_child_bound(rec, nrec, prev, v, b);
+        if (j > 0u && v != prev + 1u) b = bound_between(rec_idx, rec_t, nrec, prev, v, b);
         C.nodes++;
         if (!node_enter(S.nodes[v], ray, inv, b, par)) return false;
         prev = v;
@@ -132,17 +118,12 @@ PT_HD int qc_run(const SceneView& S, const Ray& ray, float P, int pid, F4 pre, M
             const Node nd = S.nodes[c];
             C.nodes++;
             if (!qc_slab_hit(nd, ray, inv, par)) continue;
-            const uint32_t ref = f2u(nd.b.z), cnt = f2u(nd.b.w);
-            float lt = PT_INF;
-            int lid = -1;
-            for (uint32_t i = ref; i < ref + cnt; ++i) {
-                Hit hh;
-                C.ptests++;
-                if (bvh_prim_intersect(S.prims[i], ray, hh) && hh.t < lt) { lt = hh.t; lid = (int)i; }
-            }
+            Hit lh;
+            int lid;
+            leaf_first_min(S, f2u(nd.b.z), f2u(nd.b.w), ray, lh, lid, C);
             if (lid < 0) continue;
             if (nh == 64u) { exact = true; return -1; }
-            hl[nh++] = HitLeaf{c, lt, lid};
+            hl[nh++] = HitLeaf{c, lh.t, lid};
         }
     }
     // 3: the hitting leaves in preorder
@@ -150,19 +131,15 @@ PT_HD int qc_run(const SceneView& S, const Ray& ray, float P, int pid, F4 pre, M
         for (uint32_t j = i; j > 0u && hl[j - 1].c > hl[j].c; --j) {
             const HitLeaf x = hl[j]; hl[j] = hl[j - 1]; hl[j - 1] = x;
         }
-    struct Rec {
-        uint32_t i_[64];
-        float t_[64];
-        PT_HD uint32_t idx(uint32_t r) const { return i_[r]; }
-        PT_HD float t(uint32_t r) const { return t_[r]; }
-    } rec;
+    uint32_t rec_idx[64];   // the entered hits so far, in preorder
+    float rec_t[64];
     uint32_t nrec = 0;
     float bt = PT_INF;
     int res = pid;
     for (uint32_t k = 0; k < nh; ++k) {
-        if (!qc_path_entered(S, ray, inv, par, P, hl[k].c, rec, nrec, C)) continue;
-        rec.i_[nrec] = hl[k].c;
-        rec.t_[nrec] = hl[k].t;
+        if (!qc_path_entered(S, ray, inv, par, P, hl[k].c, rec_idx, rec_t, nrec, C)) continue;
+        rec_idx[nrec] = hl[k].c;
+        rec_t[nrec] = hl[k].t;
         ++nrec;
         // 4: first strict minimum; replaces the plane hit iff strictly closer
         if (hl[k].t < bt) {

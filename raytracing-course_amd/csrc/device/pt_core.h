@@ -314,8 +314,11 @@ PT_HD bool isect_triangle(const Ray& r, f3 a, f3 b, f3 c, Hit& h) {
     return isect_triangle_n(r, a, b, c, normalize(cross(b - a, c - a)), h);
 }
 
-// src/primitives.cpp:14-52: world -> local by conj(q), test, normal back + renormalise
-PT_HD bool prim_intersect(const Prim& P, const Ray& ray, Hit& h) {
+// src/primitives.cpp:14-52: world -> local by conj(q), test, normal back + renormalise.
+// KINDS = the kinds (T_* bits) the caller's records can hold: only those are branched
+// on, in the order triangle, plane, box, ellipsoid, the last of them without a compare.
+template <uint32_t KINDS>
+PT_HD bool prim_test(const Prim& P, const Ray& ray, Hit& h) {
     const f3 pos = mk3(P.p0.x, P.p0.y, P.p0.z);
     const uint32_t type = f2u(P.p0.w);
     q4 q; q.x = P.p1.x; q.y = P.p1.y; q.z = P.p1.z; q.w = P.p1.w;
@@ -325,11 +328,11 @@ PT_HD bool prim_intersect(const Prim& P, const Ray& ray, Hit& h) {
     lr.d = qrot(cq, ray.d);
     const f3 a = mk3(P.p2.x, P.p2.y, P.p2.z);
     bool ok;
-    if (type == T_TRIANGLE) {
+    if ((KINDS & T_TRIANGLE) && (!(KINDS & (T_PLANE | T_BOX | T_ELLIPSOID)) || type == T_TRIANGLE)) {
         ok = isect_triangle(lr, a, mk3(P.p3.x, P.p3.y, P.p3.z), mk3(P.p3.w, P.p4.x, P.p4.y), h);
-    } else if (type == T_PLANE) {
+    } else if ((KINDS & T_PLANE) && (!(KINDS & (T_BOX | T_ELLIPSOID)) || type == T_PLANE)) {
         ok = isect_plane(lr, a, h);
-    } else if (type == T_BOX) {
+    } else if ((KINDS & T_BOX) && (!(KINDS & T_ELLIPSOID) || type == T_BOX)) {
         ok = isect_box(lr, a, h);
     } else {
         ok = isect_ellipsoid(lr, a, h);
@@ -337,57 +340,26 @@ PT_HD bool prim_intersect(const Prim& P, const Ray& ray, Hit& h) {
     if (ok) h.n = normalize(qrot(q, h.n));
     return ok;
 }
-
-// prim_intersect for BVH primitives (std::partition keeps planes out of the
-// BVH, src/scene.cpp:16-21): same operations without the plane branch
+// any primitive
+PT_HD bool prim_intersect(const Prim& P, const Ray& ray, Hit& h) {
+    return prim_test<T_TRIANGLE | T_PLANE | T_BOX | T_ELLIPSOID>(P, ray, h);
+}
+// a BVH primitive (std::partition keeps planes out of the BVH, src/scene.cpp:16-21)
 PT_HD bool bvh_prim_intersect(const Prim& P, const Ray& ray, Hit& h) {
-    const f3 pos = mk3(P.p0.x, P.p0.y, P.p0.z);
-    const uint32_t type = f2u(P.p0.w);
-    q4 q; q.x = P.p1.x; q.y = P.p1.y; q.z = P.p1.z; q.w = P.p1.w;
-    const q4 cq = conj(q);
-    Ray lr;
-    lr.o = qrot(cq, ray.o + -1.f * pos);
-    lr.d = qrot(cq, ray.d);
-    const f3 a = mk3(P.p2.x, P.p2.y, P.p2.z);
-    bool ok;
-    if (type == T_TRIANGLE) {
-        ok = isect_triangle(lr, a, mk3(P.p3.x, P.p3.y, P.p3.z), mk3(P.p3.w, P.p4.x, P.p4.y), h);
-    } else if (type == T_BOX) {
-        ok = isect_box(lr, a, h);
-    } else {
-        ok = isect_ellipsoid(lr, a, h);
-    }
-    if (ok) h.n = normalize(qrot(q, h.n));
-    return ok;
+    return prim_test<T_TRIANGLE | T_BOX | T_ELLIPSOID>(P, ray, h);
 }
+// a box or an ellipsoid (every emitter is one: the light distributions' tests)
+PT_HD bool solid_intersect(const Prim& P, const Ray& ray, Hit& h) { return prim_test<T_BOX | T_ELLIPSOID>(P, ray, h); }
+// a plane (the scene's plane list)
+PT_HD bool plane_intersect(const Prim& P, const Ray& ray, Hit& h) { return prim_test<T_PLANE>(P, ray, h); }
 
-// prim_intersect for a box or an ellipsoid (every emitter is one: the light distributions'
-// tests): same operations without the plane and triangle branches and their fields
-PT_HD bool solid_intersect(const Prim& P, const Ray& ray, Hit& h) {
-    const f3 pos = mk3(P.p0.x, P.p0.y, P.p0.z);
-    q4 q; q.x = P.p1.x; q.y = P.p1.y; q.z = P.p1.z; q.w = P.p1.w;
-    const q4 cq = conj(q);
-    Ray lr;
-    lr.o = qrot(cq, ray.o + -1.f * pos);
-    lr.d = qrot(cq, ray.d);
-    const f3 a = mk3(P.p2.x, P.p2.y, P.p2.z);
-    const bool ok = f2u(P.p0.w) == T_BOX ? isect_box(lr, a, h) : isect_ellipsoid(lr, a, h);
-    if (ok) h.n = normalize(qrot(q, h.n));
-    return ok;
+// A plain record's world -> local step is the identity up to the sign of zero components:
+// rotation exactly (0,0,0,1), and position +0 on every axis (the compact triangle records
+// and hit regions of the query require both).
+PT_HD bool prim_rot_identity(const Prim& P) {
+    return f2u(P.p1.x) == 0u && f2u(P.p1.y) == 0u && f2u(P.p1.z) == 0u && f2u(P.p1.w) == 0x3f800000u;
 }
-
-// plane-only form of prim_intersect (the scene's plane list): same operations
-PT_HD bool plane_intersect(const Prim& P, const Ray& ray, Hit& h) {
-    const f3 pos = mk3(P.p0.x, P.p0.y, P.p0.z);
-    q4 q; q.x = P.p1.x; q.y = P.p1.y; q.z = P.p1.z; q.w = P.p1.w;
-    const q4 cq = conj(q);
-    Ray lr;
-    lr.o = qrot(cq, ray.o + -1.f * pos);
-    lr.d = qrot(cq, ray.d);
-    if (!isect_plane(lr, mk3(P.p2.x, P.p2.y, P.p2.z), h)) return false;
-    h.n = normalize(qrot(q, h.n));
-    return true;
-}
+PT_HD bool prim_at_origin(const Prim& P) { return f2u(P.p0.x) == 0u && f2u(P.p0.y) == 0u && f2u(P.p0.z) == 0u; }
 
 // ------------------------------------------------- light distributions -----
 // src/distributions.cpp:102-110: three rng_normal calls in a row, with two copies of the polar loop where the three calls

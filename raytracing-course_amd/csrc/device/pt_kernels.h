@@ -358,7 +358,7 @@ hipError_t pt_launch_init(const pt::InitParams& p, uint32_t n_tiles, hipStream_t
 // diagnostics (PT_TUNE prespin_us): every lane busy for `us` microseconds
 hipError_t pt_launch_spin(uint32_t us, uint32_t blocks, float* sink, hipStream_t s);
 // variant: bit 0 = filtered node tests + flat replay, bit 1 = XCD-banded tile order
-hipError_t pt_launch_trace(const pt::TraceParams& p, int variant, uint32_t lds_bytes, hipStream_t s);
+hipError_t pt_launch_trace(const pt::TraceParams& p, bool fast, uint32_t lds_bytes, hipStream_t s);
 // wavefront pipeline (pt_wave.hip, pt_path.hip, pt_wcoop.hip): start a pass (first camera ray of every
 // owned pixel), then path-engine rounds
 hipError_t pt_launch_wave_start(pt::WaveParams p, hipStream_t s);

@@ -31,18 +31,15 @@ __global__ void __launch_bounds__(256) k_init(InitParams P) {
     store_sum(P.st, slot, mk3(0.f, 0.f, 0.f), ok ? y * P.tm.W + x : 0u);
 }
 
-// V bit 0: filtered node tests + flat replay loop (FAST); bit 1: XCD-banded
-// tile order -- workgroup b runs on XCD b % 8, so XCD x is given the x-th
-// contiguous band of tiles and its 4 MB L2 caches that band's working set.
-template <int V>
+// FAST: the replay's filtered node tests (bvh_replay<true>).  XCD-banded tile
+// order: workgroup b runs on XCD b % 8, so XCD x is given the x-th contiguous
+// band of tiles and its 4 MB L2 caches that band's working set.
+template <bool FAST>
 __global__ void __launch_bounds__(256) k_trace(TraceParams P) {
     extern __shared__ uint32_t lds_stack[];
-    uint32_t tile = blockIdx.x;
-    if (V & 2) {
-        const uint32_t per = (P.n_tiles_local + 7u) / 8u;
-        tile = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
-        if (tile >= P.n_tiles_local) return;
-    }
+    const uint32_t per = (P.n_tiles_local + 7u) / 8u;
+    const uint32_t tile = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
+    if (tile >= P.n_tiles_local) return;
     uint64_t t_start = 0;
     if (P.wg_prof && threadIdx.x == 0) t_start = __builtin_amdgcn_s_memrealtime();
     const uint32_t slot = tile * 256u + threadIdx.x;
@@ -62,7 +59,7 @@ __global__ void __launch_bounds__(256) k_trace(TraceParams P) {
             const float fx = fxb + rng_uniform(R);
             const float fy = fyb + rng_uniform(R);
             const Ray ray = camera_ray(P.cam, fx, fy);
-            sum = sum + trace_path<(V & 1) != 0>(P.S, P.cfg, ray, P.depth, R, stk, vs, C);
+            sum = sum + trace_path<FAST>(P.S, P.cfg, ray, P.depth, R, stk, vs, C);
         }
         hot.R = R;
         hot.done += P.spp;
@@ -168,14 +165,10 @@ hipError_t pt_launch_init(const pt::InitParams& p, uint32_t n_tiles, hipStream_t
     hipLaunchKernelGGL(pt::k_init, dim3(n_tiles), dim3(256), 0, s, p);
     return hipGetLastError();
 }
-hipError_t pt_launch_trace(const pt::TraceParams& p, int variant, uint32_t lds_bytes, hipStream_t s) {
-    const uint32_t n = p.n_tiles_local, nx = (n + 7u) / 8u * 8u;
-    switch (variant) {
-        case 0: hipLaunchKernelGGL(pt::k_trace<0>, dim3(n), dim3(256), lds_bytes, s, p); break;
-        case 1: hipLaunchKernelGGL(pt::k_trace<1>, dim3(n), dim3(256), lds_bytes, s, p); break;
-        case 2: hipLaunchKernelGGL(pt::k_trace<2>, dim3(nx), dim3(256), lds_bytes, s, p); break;
-        default: hipLaunchKernelGGL(pt::k_trace<3>, dim3(nx), dim3(256), lds_bytes, s, p); break;
-    }
+hipError_t pt_launch_trace(const pt::TraceParams& p, bool fast, uint32_t lds_bytes, hipStream_t s) {
+    const uint32_t nx = (p.n_tiles_local + 7u) / 8u * 8u;   // (whole bands: the surplus workgroups return)
+    if (fast) hipLaunchKernelGGL(pt::k_trace<true>, dim3(nx), dim3(256), lds_bytes, s, p);
+    else hipLaunchKernelGGL(pt::k_trace<false>, dim3(nx), dim3(256), lds_bytes, s, p);
     return hipGetLastError();
 }
 hipError_t pt_launch_untile(const uint8_t* in, const uint32_t* src, uint32_t tiles_x, uint32_t ww, uint32_t wh,

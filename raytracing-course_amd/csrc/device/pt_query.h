@@ -29,6 +29,14 @@
 //     recorded hit, 4 entries then their 4 records per step.
 // Rays with non-finite components, or a list full of entered hits with another
 // hit to add, take the exact stack DFS (bvh_exact) in a separate pass.
+//
+// The reference rules are pt_trace.h's: the node tests (node_enter, enter_exact,
+// enter_decide on slab_approx's interval) and the carried bound (bound_between
+// behind q_bound_between).  Stated here: the leaf check's certification margin
+// and robust crossing (q_leaf_robust), which the probe's precomputed accept
+// (q_leaf_accept_t) and the decision (q_leaf_certain) both call on slab_approx's
+// interval.  The probe's primitive test (q_exec_kind) computes t alone and is its
+// own form; plain records are recognised by pt_core.h's prim_rot_identity.
 #pragma once
 #include "pt_trace.h"
 
@@ -219,7 +227,7 @@ PT_HD void q_planes_e(const SceneView& S, const PL& pl, const Ray& ray, float& P
         const Prim pr = pl(k, pi);
         Hit h;
         bool ok;
-        if (f2u(pr.p1.x) == 0u && f2u(pr.p1.y) == 0u && f2u(pr.p1.z) == 0u && f2u(pr.p1.w) == 0x3f800000u) {
+        if (prim_rot_identity(pr)) {
             // identity rotation: the local ray equals (o - pos, d) up to the sign of
             // zero components, which changes neither the accept decision nor t
             // (a signed zero only matters in a sum that is exactly zero, where
@@ -414,35 +422,25 @@ PT_HD void q_drop_rejected(Query& q) {
 // min of the recorded hits strictly inside (a, r) (the left subtree of a when
 // r is a's right child); at least one exists when called with a = a*
 PT_HD float q_bound_between(const Query& q, uint32_t a, uint32_t r) {
-    float m = q.P;
-    bool any = false;
-#pragma unroll
-    for (int k = 0; k < PT_QHK; ++k) {
-        if ((uint32_t)k < q.ne && q.hidx[k] > a && q.hidx[k] < r) {
-            if (!any || q.ht[k] < m) m = q.ht[k];
-            any = true;
-        }
-    }
-    return m;
+    return bound_between(q.hidx, q.ht, q.ne, a, r, q.P);
+}
+
+// The certification margin m of a leaf's approximate slab interval [t1, t2] (the sum in
+// q_leaf_certain's comment), and whether the ray crosses the leaf box robustly: the
+// interval is longer than 2 margins and its exit lies beyond the margin.
+PT_HD bool q_leaf_robust(const Query& q, float t1, float t2, float& m) {
+    m = q.dl + (fabsf(t1) + fabsf(t2)) * 0x1p-18f;
+    return !q.par && t1 + m <= t2 - m && t2 - m >= 0.f;
 }
 
 // The certain-accept threshold of a leaf (q_leaf_certain's first case, computed by
-// the probe from the bundle's copy of the leaf's node record, the same floats and
-// operations): the leaf is entered whenever lo = min(P, recorded hits) >= it;
+// the probe from the bundle's copy of the leaf's node record through the same two
+// functions): the leaf is entered whenever lo = min(P, recorded hits) >= it;
 // +inf if the ray does not cross the leaf box robustly.
 PT_HD float q_leaf_accept_t(const Query& q, const F4& na, const F4& nb) {
-    const f3 c = mk3(na.x, na.y, na.z);
-    const f3 s = mk3(na.w, nb.x, nb.y);
-    const f3 o = q.ray.o + -1.f * c;
-    const f3 nlo = -1.f * s - o, nhi = s - o;
-    const float ax = nlo.x * q.inv.x, bx = nhi.x * q.inv.x;
-    const float ay = nlo.y * q.inv.y, by = nhi.y * q.inv.y;
-    const float az = nlo.z * q.inv.z, bz = nhi.z * q.inv.z;
-    const float t1 = smax(smax(smin(ax, bx), smin(ay, by)), smin(az, bz));
-    const float t2 = smin(smin(smax(ax, bx), smax(ay, by)), smax(az, bz));
-    const float m = q.dl + (fabsf(t1) + fabsf(t2)) * 0x1p-18f;
-    const bool robust = !q.par && t1 + m <= t2 - m && t2 - m >= 0.f;
-    return robust ? t1 + m : INFINITY;
+    float t1, t2, m;
+    slab_approx(na, nb, q.ray, q.inv, t1, t2);
+    return q_leaf_robust(q, t1, t2, m) ? t1 + m : INFINITY;
 }
 
 // Hitting-leaf check before any root-path replay.  Every bound the replay
@@ -466,22 +464,14 @@ PT_HD uint32_t q_leaf_certain(Query& q, const Node& nd) {
 #pragma unroll
     for (int k = 0; k < PT_QHK; ++k)
         if ((uint32_t)k < q.ne) { lo = fminf(lo, q.ht[k]); hi = fmaxf(hi, q.ht[k]); }
-    const f3 c = mk3(nd.a.x, nd.a.y, nd.a.z);
-    const f3 s = mk3(nd.a.w, nd.b.x, nd.b.y);
-    const f3 o = q.ray.o + -1.f * c;
-    const f3 nlo = -1.f * s - o, nhi = s - o;
-    const float ax = nlo.x * q.inv.x, bx = nhi.x * q.inv.x;
-    const float ay = nlo.y * q.inv.y, by = nhi.y * q.inv.y;
-    const float az = nlo.z * q.inv.z, bz = nhi.z * q.inv.z;
-    const float t1 = smax(smax(smin(ax, bx), smin(ay, by)), smin(az, bz));
-    const float t2 = smin(smin(smax(ax, bx), smax(ay, by)), smax(az, bz));
-    const float m = q.dl + (fabsf(t1) + fabsf(t2)) * 0x1p-18f;
+    float t1, t2, m;
+    slab_approx(nd.a, nd.b, q.ray, q.inv, t1, t2);
+    q.robust = q_leaf_robust(q, t1, t2, m) ? 1u : 0u;
     q.t1c = t1;
     q.mc = m;
-    q.robust = (!q.par && t1 + m <= t2 - m && t2 - m >= 0.f) ? 1u : 0u;
     if (q.robust && lo >= t1 + m) return 1u;
-    // certain reject: node_enter's decision against hi on the same quotients (its
-    // slab_approx is this computation); exact division when too close to call
+    // certain reject: node_enter's decision against hi on the same interval; exact
+    // division when too close to call
     uint32_t v = q.par ? 2u : enter_decide(t1, t2, hi);
     if (v == 2u) v = enter_exact(nd.a, nd.b, q.ray, hi) ? 1u : 0u;
     return v == 0u ? 0u : 2u;
@@ -700,9 +690,7 @@ PT_HD void q_exec_kind(const SceneView& S, Query& q, QCounts& C, Mem& stk, const
         if (full || cty != T_TRIANGLE) {
             const f3 pos = mk3(pr.p0.x, pr.p0.y, pr.p0.z);
             lr.o = q.ray.o + -1.f * pos;
-            const bool ident = f2u(pr.p1.x) == 0u && f2u(pr.p1.y) == 0u && f2u(pr.p1.z) == 0u &&
-                               f2u(pr.p1.w) == 0x3f800000u;
-            if (!ident) {
+            if (!prim_rot_identity(pr)) {
                 q4 qq;
                 qq.x = pr.p1.x; qq.y = pr.p1.y; qq.z = pr.p1.z; qq.w = pr.p1.w;
                 const q4 cq = conj(qq);

@@ -19,6 +19,15 @@
 // factors are kept in a small per-lane record stack and folded in that same
 // order, so the float result is bit-identical (no forward-throughput
 // reassociation).
+//
+// The reference rules that every query form restates live here, once each
+// (pt_query.h and pt_coop.h call them; the primitive test is pt_core.h's prim_test):
+//   node_box / node_slab     a node record's box and its exact slab test
+//   leaf_first_min           a leaf's result: first strict minimum over its primitives
+//   bound_between            a right child's bound from the recorded hits
+//   enter_exact              entered iff slab hit and not pruned, IEEE divisions
+//   slab_approx + enter_decide = node_enter   the same decision, filtered
+//   replay_enter<FAST>       bvh_replay's choice between the two
 #pragma once
 #include "pt_core.h"
 
@@ -52,6 +61,59 @@ PT_HD Ray camera_ray(const CamView& c, float x, float y) {
 
 #define PT_HITLIST 6
 
+// ---- the reference rules every query form shares, each stated once ----------
+// a node record's box: {c.xyz, s.x}, {s.yz, first/right, count} -> center c, half-size s
+PT_HD void node_box(F4 a, F4 b, f3& c, f3& s) {
+    c = mk3(a.x, a.y, a.z);
+    s = mk3(a.w, b.x, b.y);
+}
+
+// exact reference slab test of a node record: AABB_t::Intersect =
+// IntersectBox(ray + -1*center, s)  (src/bvh.cpp:89-93)
+PT_HD bool node_slab(F4 a, F4 b, const Ray& ray, float& t, uint32_t& interior) {
+    f3 c, s;
+    node_box(a, b, c, s);
+    return slab(ray.o + -1.f * c, ray.d, s, t, interior);
+}
+PT_HD bool node_slab(const Node& nd, const Ray& ray, float& t, uint32_t& interior) {
+    return node_slab(nd.a, nd.b, ray, t, interior);
+}
+
+// a leaf's result: the first strict minimum over its primitives (src/bvh.cpp:205-213;
+// lid = -1: none hit).  A reference leaf never holds a plane (bvh_prim_intersect).
+// CT = Counts or QCounts.
+template <class CT>
+PT_HD void leaf_first_min(const SceneView& S, uint32_t first, uint32_t count, const Ray& ray, Hit& best, int& lid,
+                          CT& C) {
+    best.t = PT_INF;
+    lid = -1;
+    for (uint32_t i = first; i < first + count; ++i) {
+        Hit h;
+        C.ptests++;
+        if (bvh_prim_intersect(S.prims[i], ray, h) && h.t < best.t) { best = h; lid = (int)i; }
+    }
+}
+
+// the bound a right child carries (src/bvh.cpp:216-223): the minimum over the recorded
+// hits (leaf idx[k], t[k], k < n) of its left sibling's subtree -- the leaves strictly
+// inside (lo, hi) = (parent, right child) in the preorder layout -- if there is one,
+// else `dflt`, the parent's bound.  (An unrolled scan of all N slots: the lists stay in
+// registers.)
+template <int N>
+PT_HD float bound_between(const uint32_t (&idx)[N], const float (&t)[N], uint32_t n, uint32_t lo, uint32_t hi,
+                          float dflt) {
+    float m = dflt;
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        if ((uint32_t)k < n && idx[k] > lo && idx[k] < hi) {
+            if (!any || t[k] < m) m = t[k];
+            any = true;
+        }
+    }
+    return m;
+}
+
 // Exact reference traversal.  `stk` is per-lane word memory: set(i, v) / get(i).
 template <class Stack>
 PT_HD int bvh_exact(const SceneView& S, const Ray& ray, float cb, Stack& stk, Hit& best, Counts& C) {
@@ -66,25 +128,16 @@ PT_HD int bvh_exact(const SceneView& S, const Ray& ray, float cb, Stack& stk, Hi
     for (;;) {
         const Node nd = S.nodes[node];
         C.nodes++;
-        const f3 c = mk3(nd.a.x, nd.a.y, nd.a.z);
-        const f3 s = mk3(nd.a.w, nd.b.x, nd.b.y);
         float t;
         uint32_t interior;
-        // AABB_t::Intersect: IntersectBox(ray + -1*center, s)  (src/bvh.cpp:89-93)
-        const bool hit = slab(ray.o + -1.f * c, ray.d, s, t, interior);
+        const bool hit = node_slab(nd, ray, t, interior);
         bool descend = false;
         if (hit && !(cb < t && !interior)) {
             const uint32_t ref = f2u(nd.b.z), cnt = f2u(nd.b.w);
             if (!(cnt & PT_NODE_INTERIOR)) {
-                // leaf: first-min over its primitives (strict <), src/bvh.cpp:205-213
                 Hit lb;
-                lb.t = PT_INF;
-                int lid = -1;
-                for (uint32_t i = ref; i < ref + cnt; ++i) {
-                    Hit h;
-                    C.ptests++;
-                    if (prim_intersect(S.prims[i], ray, h) && h.t < lb.t) { lb = h; lid = (int)i; }
-                }
+                int lid;
+                leaf_first_min(S, ref, cnt, ray, lb, lid, C);
                 if (lid >= 0) {
                     // append to the monotone suffix-minimum list
                     uint32_t keep = 0;
@@ -158,30 +211,12 @@ PT_HD bool aux_box(float lx, float ly, float lz, float hx, float hy, float hz, f
     return tn <= tf && tf >= 0.f;
 }
 
-// exact reference slab test of node `n` (AABB_t::Intersect, src/bvh.cpp:89-93)
-PT_HD bool node_slab(const Node& nd, const Ray& ray, float& t, uint32_t& interior) {
-    const f3 c = mk3(nd.a.x, nd.a.y, nd.a.z);
-    const f3 s = mk3(nd.a.w, nd.b.x, nd.b.y);
-    return slab(ray.o + -1.f * c, ray.d, s, t, interior);
-}
-
-// Filtered exact node test.  Decides exactly what node_slab + the reference's
-// prune rule decide -- hit iff !(t1 > t2) && !(t2 < 0); pruned iff
-// bound < t1 && !(t1 < 0) -- but evaluates the six quotients (+-s - o)/d as
-// (+-s - o) * rinv with rinv = 1/d (IEEE, once per ray) instead of six IEEE
-// divisions.  Both quotient forms are within 1.5 ulp of the real quotient
-// (rinv rel. error <= 2^-24, product rounding <= 2^-24; the IEEE quotient
-// <= 2^-24), min/max selection is monotone in both, so every compared value
-// is within E = |v| 2^-20 + 1e-30 of its exact counterpart.  A decision whose
-// operands are closer than that margin is re-done with the exact division
-// (slab()).  Requires replay_ok_ray(ray) (finite, non-tiny d: |rinv| < 1e30).
-// Returns true iff the node is entered (hit and not pruned).
-// exact = true: always the IEEE-division form (rays with near-zero direction components).
-// approximate slab interval of a (center, half-size) box: the reference's
-// numerators (same IEEE ops) times the per-ray reciprocal
+// approximate slab interval of a node record's box: the reference's numerators
+// (same IEEE ops) times the per-ray reciprocal.  THE interval of every filtered
+// decision: node_enter, qc_slab_hit, q_leaf_accept_t, q_leaf_certain.
 PT_HD void slab_approx(F4 a, F4 b, const Ray& ray, f3 rinv, float& t1, float& t2) {
-    const f3 c = mk3(a.x, a.y, a.z);
-    const f3 s = mk3(a.w, b.x, b.y);
+    f3 c, s;
+    node_box(a, b, c, s);
     const f3 o = ray.o + -1.f * c;                 // src/bvh.cpp:92 (same IEEE adds)
     const f3 nlo = -1.f * s - o, nhi = s - o;      // src/primitives.cpp:71-72 numerators
     const float ax = nlo.x * rinv.x, bx = nhi.x * rinv.x;
@@ -211,14 +246,24 @@ PT_HD uint32_t enter_decide(float t1, float t2, float bound) {
 
 // the exact decision (IEEE division, the reference's slab)
 PT_HD bool enter_exact(F4 a, F4 b, const Ray& ray, float bound) {
-    const f3 c = mk3(a.x, a.y, a.z);
-    const f3 s = mk3(a.w, b.x, b.y);
     float t;
     uint32_t in;
-    if (!slab(ray.o + -1.f * c, ray.d, s, t, in)) return false;
+    if (!node_slab(a, b, ray, t, in)) return false;
     return !(bound < t && !in);
 }
 
+// Filtered exact node test.  Decides exactly what node_slab + the reference's
+// prune rule decide -- hit iff !(t1 > t2) && !(t2 < 0); pruned iff
+// bound < t1 && !(t1 < 0) -- but evaluates the six quotients (+-s - o)/d as
+// (+-s - o) * rinv with rinv = 1/d (IEEE, once per ray) instead of six IEEE
+// divisions.  Both quotient forms are within 1.5 ulp of the real quotient
+// (rinv rel. error <= 2^-24, product rounding <= 2^-24; the IEEE quotient
+// <= 2^-24), min/max selection is monotone in both, so every compared value
+// is within E = |v| 2^-20 + 1e-30 of its exact counterpart.  A decision whose
+// operands are closer than that margin is re-done with the exact division
+// (slab()).  Requires replay_ok_ray(ray) (finite, non-tiny d: |rinv| < 1e30).
+// Returns true iff the node is entered (hit and not pruned).
+// exact = true: always the IEEE-division form (rays with near-zero direction components).
 PT_HD bool node_enter(const Node& nd, const Ray& ray, f3 rinv, float bound, bool exact = false) {
     float t1, t2;
     slab_approx(nd.a, nd.b, ray, rinv, t1, t2);
@@ -260,9 +305,16 @@ PT_HD bool replay_ok_ray(const Ray& r) {
            fabsf(r.o.z) < big;
 }
 
+// bvh_replay's node test: entered iff slab hit and not pruned by `bound`.  FAST: the
+// filtered form (node_enter); otherwise always the reference's IEEE divisions.  Both
+// decide the same, so both forms of the replay test the same nodes in the same order.
+template <bool FAST>
+PT_HD bool replay_enter(const Node& nd, const Ray& ray, f3 rinv, float bound) {
+    return FAST ? node_enter(nd, ray, rinv, bound) : enter_exact(nd.a, nd.b, ray, bound);
+}
+
 // returns best hit id (-1 none); sets `fallback` when the exact DFS must be used instead.
-// FAST: filtered node tests (node_enter) and one flat replay loop over all
-// (candidate, ancestor) steps; otherwise the IEEE-division reference form.
+// One flat replay loop over all (candidate, ancestor) steps; FAST selects the node test.
 template <bool FAST, class Mem>
 PT_HD int bvh_replay(const SceneView& S, const ReplayCfg& cfg, const Ray& ray, float P, Mem& L, Hit& best,
                      Counts& C, bool& fallback) {
@@ -297,13 +349,7 @@ PT_HD int bvh_replay(const SceneView& S, const ReplayCfg& cfg, const Ray& ray, f
                     const uint32_t leaf = code & 0x7fffffffu;
                     if (leaf < lb) continue;
                     C.nodes++;
-                    if (FAST) {
-                        if (!node_enter(S.nodes[leaf], ray, inv, PT_INF)) continue;
-                    } else {
-                        float t;
-                        uint32_t in;
-                        if (!node_slab(S.nodes[leaf], ray, t, in)) continue;
-                    }
+                    if (!replay_enter<FAST>(S.nodes[leaf], ray, inv, PT_INF)) continue;   // (no bound: slab hit)
                     if (n < cfg.cap) {
                         L.set(cfg.as + n, leaf);
                         if (leaf > mx || n == 0) { mx = leaf; mxpos = n; }
@@ -343,119 +389,46 @@ PT_HD int bvh_replay(const SceneView& S, const ReplayCfg& cfg, const Ray& ray, f
             L.set(cfg.as + j, v);
         }
         // ---- replay root -> candidate paths in preorder
+        // (one flat loop: each iteration tests one node of the current candidate's root path)
         uint32_t skip = lb;
-        if (FAST) {
-            // one flat loop: each iteration tests one node of the current candidate's root path
-            uint32_t k = 0, cand = 0;
-            while (k < n && (cand = L.get(cfg.as + k)) < skip) ++k;
-            uint32_t a = 0;
-            float bound = P;
-            while (k < n) {
-                const Node nd = S.nodes[a];
-                C.nodes++;
-                const uint32_t ref = f2u(nd.b.z), info = f2u(nd.b.w);
-                bool next_cand = false;
-                if (!node_enter(nd, ray, inv, bound)) {
-                    skip = (info & PT_NODE_INTERIOR) ? (info & 0x7fffffffu) : a + 1u;
-                    next_cand = true;
-                } else if (a == cand) {
-                    // leaf reached: first-min over its primitives (src/bvh.cpp:205-213)
-                    Hit lbh;
-                    lbh.t = PT_INF;
-                    int lid = -1;
-                    for (uint32_t i = ref; i < ref + info; ++i) {
-                        Hit h;
-                        C.ptests++;
-                        if (prim_intersect(S.prims[i], ray, h) && h.t < lbh.t) { lbh = h; lid = (int)i; }
-                    }
-                    if (lid >= 0) {
-                        if (nh == PT_REPLAY_HITS) { fallback = true; return -1; }
+        uint32_t k = 0, cand = 0;
+        while (k < n && (cand = L.get(cfg.as + k)) < skip) ++k;
+        uint32_t a = 0;
+        float bound = P;
+        while (k < n) {
+            const Node nd = S.nodes[a];
+            C.nodes++;
+            const uint32_t ref = f2u(nd.b.z), info = f2u(nd.b.w);
+            bool next_cand = false;
+            if (!replay_enter<FAST>(nd, ray, inv, bound)) {
+                skip = (info & PT_NODE_INTERIOR) ? (info & 0x7fffffffu) : a + 1u;
+                next_cand = true;
+            } else if (a == cand) {
+                // leaf reached
+                Hit lbh;
+                int lid;
+                leaf_first_min(S, ref, info, ray, lbh, lid, C);
+                if (lid >= 0) {
+                    if (nh == PT_REPLAY_HITS) { fallback = true; return -1; }
 #pragma unroll
-                        for (int q = 0; q < PT_REPLAY_HITS; ++q)
-                            if ((uint32_t)q == nh) { h_idx[q] = cand; h_t[q] = lbh.t; }
-                        ++nh;
-                        if (lbh.t < best.t) { best = lbh; best_id = lid; }
-                    }
-                    skip = cand + 1u;
-                    next_cand = true;
-                } else if (cand < ref) {
-                    a = a + 1u;                      // left child: same bound
-                } else {
-                    // right child: bound = best hit of the left sibling's subtree, if any
-                    float m = bound;
-                    bool any = false;
-#pragma unroll
-                    for (int q = 0; q < PT_REPLAY_HITS; ++q) {
-                        if ((uint32_t)q < nh && h_idx[q] > a && h_idx[q] < ref) {
-                            if (!any || h_t[q] < m) m = h_t[q];
-                            any = true;
-                        }
-                    }
-                    bound = m;
-                    a = ref;
+                    for (int q = 0; q < PT_REPLAY_HITS; ++q)
+                        if ((uint32_t)q == nh) { h_idx[q] = cand; h_t[q] = lbh.t; }
+                    ++nh;
+                    if (lbh.t < best.t) { best = lbh; best_id = lid; }
                 }
-                if (next_cand) {
-                    ++k;
-                    while (k < n && (cand = L.get(cfg.as + k)) < skip) ++k;
-                    a = 0;
-                    bound = P;
-                }
+                skip = cand + 1u;
+                next_cand = true;
+            } else if (cand < ref) {
+                a = a + 1u;                      // left child: same bound
+            } else {
+                bound = bound_between(h_idx, h_t, nh, a, ref, bound);   // right child
+                a = ref;
             }
-        } else {
-            for (uint32_t k = 0; k < n; ++k) {
-                const uint32_t cand = L.get(cfg.as + k);
-                if (cand < skip) continue;
-                uint32_t a = 0;
-                float bound = P;
-                for (;;) {
-                    const Node nd = S.nodes[a];
-                    C.nodes++;
-                    float t;
-                    uint32_t in;
-                    const bool hit = node_slab(nd, ray, t, in);
-                    const uint32_t ref = f2u(nd.b.z), info = f2u(nd.b.w);
-                    if (!hit || (bound < t && !in)) {
-                        skip = (info & PT_NODE_INTERIOR) ? (info & 0x7fffffffu) : a + 1u;
-                        break;
-                    }
-                    if (a == cand) {
-                        // leaf reached: first-min over its primitives (src/bvh.cpp:205-213)
-                        Hit lbh;
-                        lbh.t = PT_INF;
-                        int lid = -1;
-                        for (uint32_t i = ref; i < ref + info; ++i) {
-                            Hit h;
-                            C.ptests++;
-                            if (prim_intersect(S.prims[i], ray, h) && h.t < lbh.t) { lbh = h; lid = (int)i; }
-                        }
-                        if (lid >= 0) {
-                            if (nh == PT_REPLAY_HITS) { fallback = true; return -1; }
-#pragma unroll
-                            for (int q = 0; q < PT_REPLAY_HITS; ++q)
-                                if ((uint32_t)q == nh) { h_idx[q] = cand; h_t[q] = lbh.t; }
-                            ++nh;
-                            if (lbh.t < best.t) { best = lbh; best_id = lid; }
-                        }
-                        skip = cand + 1u;
-                        break;
-                    }
-                    if (cand < ref) {
-                        a = a + 1u;                      // left child: same bound
-                    } else {
-                        // right child: bound = best hit of the left sibling's subtree, if any
-                        float m = bound;
-                        bool any = false;
-#pragma unroll
-                        for (int q = 0; q < PT_REPLAY_HITS; ++q) {
-                            if ((uint32_t)q < nh && h_idx[q] > a && h_idx[q] < ref) {
-                                if (!any || h_t[q] < m) m = h_t[q];
-                                any = true;
-                            }
-                        }
-                        bound = m;
-                        a = ref;
-                    }
-                }
+            if (next_cand) {
+                ++k;
+                while (k < n && (cand = L.get(cfg.as + k)) < skip) ++k;
+                a = 0;
+                bound = P;
             }
         }
         if (!overflow) break;

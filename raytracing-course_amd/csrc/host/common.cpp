@@ -118,6 +118,8 @@ const Rccl& rccl() {
 //   cprof=1           per-phase cycles of the cooperative engine on stderr (-DPT_CPROF builds)
 //   qstats=FILE       per-query work counters of the host self-test render
 //   qengine=coop      host self-tests: the cooperative engine's query algorithm (pt_coop.h)
+//   qengine=mega      host self-tests, traversal 0: the megakernel's query with the filtered node
+//                     tests (ray_intersection<true>, the code of engine=mega's k_trace)
 //   prepstats=1       pt_scene_prepare's per-stage times on stderr
 std::string tune_str(const char* key) {
     // the single-variable switches of earlier builds are ignored now: say so once

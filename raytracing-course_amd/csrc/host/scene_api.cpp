@@ -118,10 +118,7 @@ bool leaf_hit_region(const pt_scene* s, uint32_t leaf, float lo[3], float hi[3])
     double l[3] = {INFINITY, INFINITY, INFINITY}, h[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (uint32_t i = first; i < first + cnt; ++i) {
         const pt::Prim& P = s->dprims.at(i);
-        const bool plain = pt::f2u(P.p0.w) == pt::T_TRIANGLE && pt::f2u(P.p0.x) == 0u && pt::f2u(P.p0.y) == 0u &&
-                           pt::f2u(P.p0.z) == 0u && pt::f2u(P.p1.x) == 0u && pt::f2u(P.p1.y) == 0u &&
-                           pt::f2u(P.p1.z) == 0u && pt::f2u(P.p1.w) == 0x3f800000u;
-        if (!plain) return false;
+        if (!(pt::f2u(P.p0.w) == pt::T_TRIANGLE && pt::prim_at_origin(P) && pt::prim_rot_identity(P))) return false;
         const pt::f3 a = pt::mk3(P.p2.x, P.p2.y, P.p2.z), b = pt::mk3(P.p3.x, P.p3.y, P.p3.z),
                      c = pt::mk3(P.p3.w, P.p4.x, P.p4.y);
         const pt::f3 nf = pt::normalize(pt::cross(b - a, c - a));   // the test's own float normal
@@ -319,11 +316,8 @@ void build_query_blob(pt_scene* s, const std::function<void(const char*)>& tick)
     for (size_t i = i0; i < i1; ++i) {
         const pt::Prim& P = s->dprims[i];
         const uint32_t type = pt::f2u(P.p0.w);
-        const bool pos0 = pt::f2u(P.p0.x) == 0u && pt::f2u(P.p0.y) == 0u && pt::f2u(P.p0.z) == 0u;
-        const bool rot1 = pt::f2u(P.p1.x) == 0u && pt::f2u(P.p1.y) == 0u && pt::f2u(P.p1.z) == 0u &&
-                          pt::f2u(P.p1.w) == 0x3f800000u;
         pt::F4* r = &qp[4 * i];
-        if (type == pt::T_TRIANGLE && pos0 && rot1) {
+        if (type == pt::T_TRIANGLE && pt::prim_at_origin(P) && pt::prim_rot_identity(P)) {
             // with the triangle's normal exactly as IntersectTriangle computes it
             const pt::f3 a = pt::mk3(P.p2.x, P.p2.y, P.p2.z), b = pt::mk3(P.p3.x, P.p3.y, P.p3.z),
                          c = pt::mk3(P.p3.w, P.p4.x, P.p4.y);

@@ -41,13 +41,16 @@ int pt_selftest_ray_intersection(pt_scene* s, int32_t traversal, uint32_t n, con
     HostStack stk;
     pt::Counts C{};
     const bool coop = tune_str("qengine") == "coop";   // the cooperative engine's query (pt_coop.h)
+    const bool mega = tune_str("qengine") == "mega";   // the megakernel's FAST query (k_trace<true>)
     for (uint32_t i = 0; i < n; ++i) {
         pt::Ray r;
         r.o = pt::mk3(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]);
         r.d = pt::mk3(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
         pt::Hit h;
         int id;
-        if (traversal == PT_TRAVERSAL_REPLAY) {
+        if (traversal == PT_TRAVERSAL_REPLAY && mega) {
+            id = pt::ray_intersection<true>(V, cfg, r, stk, h, C);
+        } else if (traversal == PT_TRAVERSAL_REPLAY) {
             pt::QCounts Q{0u, 0u, 0u, 0u};
             uint32_t ex = 0;
             id = coop ? pt::qc_query(V, r, stk, h, Q, ex) : pt::q_run(V, r, stk, h, Q, ex);
@@ -90,6 +93,7 @@ int pt_selftest_render_host(pt_scene* s, int32_t traversal, uint32_t x0, uint32_
     const char* qpath = qpaths.empty() ? nullptr : qpaths.c_str();
     std::vector<std::vector<std::array<uint32_t, 4>>> qlogs(nt);
     const bool coop = tune_str("qengine") == "coop";   // the cooperative engine's query (pt_coop.h)
+    const bool mega = tune_str("qengine") == "mega";   // the megakernel's FAST query (k_trace<true>)
     for (uint32_t t = 0; t < nt; ++t) {
         th.emplace_back([&, t]() {
             std::vector<std::array<uint32_t, 4>>* qlog = qpath ? &qlogs[t] : nullptr;
@@ -104,7 +108,9 @@ int pt_selftest_render_host(pt_scene* s, int32_t traversal, uint32_t x0, uint32_
                     const float fx = (float)x + pt::rng_uniform(R);
                     const float fy = (float)y + pt::rng_uniform(R);
                     const pt::Ray ray = pt::camera_ray(cam, fx, fy);
-                    if (traversal == PT_TRAVERSAL_REPLAY) {
+                    if (traversal == PT_TRAVERSAL_REPLAY && mega) {
+                        sum = sum + pt::trace_path<true>(V, cfg, ray, s->hs.depth, R, stk, vs, C);
+                    } else if (traversal == PT_TRAVERSAL_REPLAY) {
                         // the wavefront engine's query (pt_query.h state machine), run to completion
                         auto q = [&](const pt::Ray& rr, pt::Hit& hh, pt::Counts& cc) {
                             pt::QCounts Q{};

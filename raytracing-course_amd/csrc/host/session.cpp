@@ -413,8 +413,8 @@ int pt_session_trace(pt_session* ss, uint32_t spp) {
     tp.spp = spp;
     tp.n_tiles_local = ss->n_tiles_local;
     tp.wg_prof = nullptr;
-    // kernel variant: filtered tests unless the division form was asked for; XCD-banded tile order
-    const int variant = (ss->traversal == PT_TRAVERSAL_REPLAY ? 1 : 0) | 2;
+    // filtered node tests unless the division form was asked for
+    const bool fast = ss->traversal == PT_TRAVERSAL_REPLAY;
     const std::string wgps = tune_str("wgprof");
     const char* wgp = wgps.c_str();
     if (*wgp) {
@@ -428,7 +428,7 @@ int pt_session_trace(pt_session* ss, uint32_t spp) {
     HIP_TRY(hipEventCreate(&e0));
     HIP_TRY(hipEventCreate(&e1));
     HIP_TRY(hipEventRecord(e0, ss->stream));
-    HIP_TRY(pt_launch_trace(tp, variant, lds, ss->stream));
+    HIP_TRY(pt_launch_trace(tp, fast, lds, ss->stream));
     HIP_TRY(hipEventRecord(e1, ss->stream));
     if (tp.wg_prof) {
         // diagnostics: append this launch's per-workgroup timeline to the wgprof file

@@ -213,8 +213,10 @@ class Scene:
         return nb.tobytes(), pb.tobytes()
 
     def render(self, device=0, ngpu=1, samples=0, spp_per_launch=0, radiance=False, progress=False, window=None,
-               traversal=TRAVERSAL_REPLAY, gather=GATHER_AUTO):
+               traversal=TRAVERSAL_REPLAY, gather=GATHER_AUTO, check=True):
         """Render on the GPU(s): returns (rgb u8 HxWx3, radiance f32 HxWx3 | None, stats).
+        check=False: a tripped exactness guard (stats["errors"] != 0, the render's error) does
+        not raise.
 
         window=(x0, y0, w, h) renders only those pixels (global-index seeds kept).
         gather: GATHER_AUTO (RCCL when ngpu > 1), GATHER_RCCL (RCCL at any ngpu, an
@@ -231,7 +233,9 @@ class Scene:
         if window:
             o.win_x0, o.win_y0, o.win_w, o.win_h = window
         st = Stats()
-        _check(_lib.pt_render(self._h, C.byref(o), _ptr(rgb), _ptr(rad), C.byref(st)))
+        rc = _lib.pt_render(self._h, C.byref(o), _ptr(rgb), _ptr(rad), C.byref(st))
+        if check or not st.errors:
+            _check(rc)
         return rgb, rad, st.as_dict()
 
     def intersect(self, rays, device=0):
@@ -246,15 +250,19 @@ class Scene:
         return hits, st.as_dict()
 
     # test hooks (host execution of the device traversal code; not a render path)
-    def selftest_ray_intersection(self, rays, traversal=TRAVERSAL_REPLAY):
+    def selftest_ray_intersection(self, rays, traversal=TRAVERSAL_REPLAY, check=True):
+        """check=False: a hit-list overflow (the exact DFS's counted condition: the call's error)
+        does not raise; the counters' "errors" holds it"""
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         ids = np.zeros(len(rays), np.int32)
         hits = np.zeros((len(rays), 5), np.float32)
         ctr = np.zeros(8, np.uint64)
-        _check(_lib.pt_selftest_ray_intersection(self._h, traversal, len(rays), _ptr(rays), _ptr(ids), _ptr(hits),
-                                                 _ptr(ctr)))
+        rc = _lib.pt_selftest_ray_intersection(self._h, traversal, len(rays), _ptr(rays), _ptr(ids), _ptr(hits),
+                                               _ptr(ctr))
+        if check or not ctr[CTR_ERRORS]:
+            _check(rc)
         return ids, hits, {"nodes": int(ctr[CTR_NODES]), "prim_tests": int(ctr[CTR_PTESTS]), "aux": int(ctr[CTR_AUX]),
-                           "fallbacks": int(ctr[CTR_FALLBACKS])}
+                           "fallbacks": int(ctr[CTR_FALLBACKS]), "errors": int(ctr[CTR_ERRORS])}
 
     def selftest_render_host(self, x0, y0, w, h, spp=0, traversal=TRAVERSAL_REPLAY):
         rad = np.zeros((h, w, 3), np.float32)

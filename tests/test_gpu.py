@@ -261,12 +261,15 @@ def test_exact_handover_beyond_the_query_lanes(pt, monkeypatch):
     assert np.array_equal(rgb, ref)
 
 
-def test_megakernel_engine_bit_exact(pt, monkeypatch):
+@pytest.mark.parametrize("name", ["dragon_64x64x16", "mat_matrix_24x24x8", "rabbid_48x48x4", "hw3s4_48x48x8"])
+def test_megakernel_engine_bit_exact(pt, name, monkeypatch):
     """PT_TUNE engine=mega: the megakernel (one lane per pixel, whole paths) on the
-    replay traversal gives the same bytes as the path engine"""
+    replay traversal (k_trace<true>: bvh_replay with the filtered node tests) gives the
+    reference's bytes, as the path engine does.  (The 60-triangle stack scene, on which its
+    replay hands rays over to the exact DFS, is in tests/test_query_step.py.)"""
     monkeypatch.setenv("PT_TUNE", "engine=mega")
-    m, img, rad = U.golden_image("dragon_64x64x16")
-    with pt.Scene.load(U.golden_scene_path("dragon_64x64x16")) as s:
+    m, img, rad = U.golden_image(name)
+    with pt.Scene.load(U.golden_scene_path(name)) as s:
         rgb, r, st = s.render(radiance=True, traversal=0)
     assert st["rounds"] == 0 and st["errors"] == 0
     assert r.view(np.uint32).tolist() == rad.view(np.uint32).tolist()

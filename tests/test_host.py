@@ -205,9 +205,15 @@ HOST_RENDER = ["p51_64x48x16", "p52_64x48x16", "dragon_metal_64x64x8", "dragon_g
                "hw3s4_48x48x8", "hw3s5_48x48x8", "rabbid_48x48x4", "c2_win_240_200_24x24"]
 
 
-@pytest.mark.parametrize("trav", sorted(TRAVERSALS))
-@pytest.mark.parametrize("name", HOST_RENDER)
-def test_device_integrator_on_host_bit_exact(name, trav):
+# every traversal on every fixture; on the first nine also the megakernel's query with the
+# filtered node tests (PT_TUNE qengine=mega: bvh_replay<true>, the code of engine=mega's k_trace)
+HOST_FORMS = [(n, t) for n in HOST_RENDER for t in sorted(TRAVERSALS)] + [(n, "mega") for n in HOST_RENDER[:9]]
+
+
+@pytest.mark.parametrize("name,trav", HOST_FORMS)
+def test_device_integrator_on_host_bit_exact(name, trav, monkeypatch):
+    if trav == "mega":
+        monkeypatch.setenv("PT_TUNE", "qengine=mega")
     m, img, rad = U.golden_image(name)
     with pt.Scene.load(U.golden_scene_path(name)) as s:
         s.prepare()
@@ -215,7 +221,7 @@ def test_device_integrator_on_host_bit_exact(name, trav):
             x0, y0, w, h = m["window"]
         else:
             x0, y0, h, w = 0, 0, img.shape[0], img.shape[1]
-        got = s.selftest_render_host(x0, y0, w, h, traversal=TRAVERSALS[trav])
+        got = s.selftest_render_host(x0, y0, w, h, traversal=TRAVERSALS.get(trav, 0))
     assert got.view(np.uint32).tolist() == rad.view(np.uint32).tolist()
     assert np.array_equal(U.oracle_tonemap(got).reshape(img.shape), img)
 

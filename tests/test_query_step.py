@@ -18,6 +18,11 @@ this file was added (e21e197), through the host execution of the same state mach
 over anything else moves one of them.  The GPU tests run the same rays through k_rays /
 k_rays_exact and compare with the same answers and the host's counters, and render the
 dragon fixture on the path engine alone (k_wpath).
+
+The other query forms (bvh_exact, both forms of bvh_replay, qc_run) share the reference rules
+with the state machine, each rule one function: the same rays go through
+them too, with their own recorded counters (FORM_COUNTERS), and the megakernel renders the
+stack scene on the GPU.
 """
 from concurrent.futures import ThreadPoolExecutor
 
@@ -166,12 +171,12 @@ def tmp_root(tmp_path_factory):
     return tmp_path_factory.mktemp("query_step")
 
 
-def host_query(name, tmp_root):
+def host_query(name, tmp_root, traversal=0, check=True):
     pt = U.ptrace()
     path, rays, oids, ohits = ray_set(name, tmp_root)
     with pt.Scene.load(path) as s:
         s.prepare()
-        ids, hits, ctr = s.selftest_ray_intersection(rays, traversal=0)
+        ids, hits, ctr = s.selftest_ray_intersection(rays, traversal=traversal, check=check)
     print("%s: %d rays, %d hits, counters %r" % (name, len(rays), int((oids != -1).sum()),
                                                (ctr["nodes"], ctr["prim_tests"], ctr["aux"], ctr["fallbacks"])))
     assert np.array_equal(ids, oids)
@@ -230,6 +235,70 @@ def test_bulk_rays_on_the_dragon_fixture(tmp_root, name):
     assert_parent_counters(name, ctr)
 
 
+# ---- host: the other query forms on the same rays ------------------------------------------
+# form: (traversal, PT_TUNE).  exact = bvh_exact alone; replay_div = bvh_replay<false> (+ bvh_exact
+# for the rays it hands over); coop = the cooperative engine's qc_run; mega = bvh_replay<true>,
+# the megakernel's query with the filtered node tests
+FORMS = {"exact": (1, None), "replay_div": (2, None), "coop": (0, "qengine=coop"), "mega": (0, "qengine=mega")}
+
+# {form: {set: (nodes, prim_tests, aux, fallbacks)}} of selftest_ray_intersection in that form,
+# recorded from the build of commit 2ca9185 (the parent of the commit that made each reference
+# rule of the query code one function) plus that commit's qengine=mega hook and nothing else.
+# mega has no row: it makes the decisions of replay_div (the filtered node test decides what the
+# division form decides), so its counters must equal replay_div's.
+FORM_COUNTERS = {
+    "exact": {
+        "stack": (36852, 16607, 0, 0),
+        "stack_few": (5668, 2644, 0, 0),
+        "zero": (384, 75, 0, 0),
+        "wide": (307464, 916, 0, 0),
+        "bulk1": (20932326, 27558, 0, 0),
+        "bulk2": (9348892, 172941, 0, 0),
+    },
+    "replay_div": {
+        "stack": (133774, 19789, 59155, 151),
+        "stack_few": (23196, 2644, 8256, 0),
+        "zero": (384, 75, 0, 384),
+        "wide": (17496, 916, 6295, 0),
+        "bulk1": (558539, 27558, 250713, 0),
+        "bulk2": (3251292, 172941, 74157, 816),
+    },
+    "coop": {
+        "stack": (72106, 19658, 10242, 0),
+        "stack_few": (3217, 1834, 1122, 0),
+        "zero": (119, 82, 384, 0),
+        "wide": (1036, 916, 3036, 0),
+        "bulk1": (13676, 4062, 93824, 0),
+        "bulk2": (394189, 166140, 46174, 32),
+    },
+}
+FORM_COUNTERS["mega"] = FORM_COUNTERS["replay_div"]
+
+
+@pytest.mark.parametrize("form", sorted(FORMS))
+@pytest.mark.parametrize("name", ["stack", "stack_few", "zero", "wide", "bulk1", "bulk2"])
+def test_other_query_forms_same_answers_and_parent_counters(tmp_root, monkeypatch, name, form):
+    """bvh_exact, both forms of bvh_replay and qc_run share the leaf result (leaf_first_min),
+    the carried bound (bound_between) and the node tests with the state machine: the oracle's
+    answers (checked in host_query) and, per form, the work the parent commit's copies did.
+    The stack set's rays with more than six hitting leaves take bvh_replay's hand-over and
+    bvh_exact's suffix-minimum list.  On 32 of them that six-entry list itself overflows
+    (seven leaf hits in a row, each farther than the last): bvh_exact counts it and the forms
+    that run it under their own counters (all but coop and the state machine, whose q_exact
+    keeps a private count) report "hit list overflow", as the parent commit's build does.
+    The answers are still the oracle's and the work is still the parent's: both are checked,
+    with the reported condition pinned too."""
+    traversal, tune = FORMS[form]
+    if tune:
+        monkeypatch.setenv("PT_TUNE", tune)
+    overflows = name == "stack" and form != "coop"
+    _, _, ctr = host_query(name, tmp_root, traversal, check=not overflows)
+    assert ctr["errors"] == (1 if overflows else 0)
+    if name == "stack" and form in ("replay_div", "mega"):
+        assert ctr["fallbacks"] > 0
+    assert (ctr["nodes"], ctr["prim_tests"], ctr["aux"], ctr["fallbacks"]) == FORM_COUNTERS[form][name]
+
+
 # ---- GPU: the same rays through k_rays / k_rays_exact, and the path engine --------------------
 @pytest.fixture(scope="module")
 def gpu_pt():
@@ -263,6 +332,35 @@ def test_ray_queries_match_the_oracle_and_the_host_counters(gpu_pt, tmp_root, na
     assert (st["node_visits"], st["prim_tests"], st["aux_visits"], st["fallbacks"]) == \
         (host["nodes"], host["prim_tests"], host["aux"], host["fallbacks"])
     assert_parent_counters(name, host)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", ["engine_mega", "replay_div"])
+def test_megakernel_renders_the_stack_scene_through_the_handover(gpu_pt, tmp_root, monkeypatch, form):
+    """The stack scene itself (8x8 pixels, 1 spp, depth 1) on the megakernel: k_trace<true>
+    (PT_TUNE engine=mega, traversal 0) and k_trace<false> (traversal 2).  It is the smallest
+    shape on which bvh_replay's one loop hands rays over to bvh_exact on the device (more
+    than six hitting leaves).  The scene has no light, so the oracle's image is black: what
+    the case shows is that the hand-over runs, ends and counts every ray.  As on the host
+    (test_other_query_forms_...), bvh_exact's own six-entry list overflows on camera rays
+    down the stack, which the megakernel reports (the render's exactness guard, as in the
+    parent commit's build): pinned here, not raised."""
+    pt = gpu_pt
+    path = ray_set("stack", tmp_root)[0]
+    if form == "engine_mega":
+        monkeypatch.setenv("PT_TUNE", "engine=mega")
+    orgb, orad, octr = U.OracleScene(path).render()
+    with pt.Scene.load(path) as s:
+        s.prepare()
+        rgb, r, st = s.render(radiance=True, traversal=0 if form == "engine_mega" else 2, check=False)
+    print("stack scene, %s: %r" % (form, {k: st[k] for k in ("rays", "node_visits", "prim_tests", "aux_visits",
+                                                             "fallbacks", "errors", "rounds")}))
+    assert rgb.shape == (8, 8, 3) and st["rounds"] == 0 and st["short_pixels"] == 0
+    assert st["fallbacks"] > 0
+    assert st["errors"] > 0
+    assert np.array_equal(r.view(np.uint32), orad.view(np.uint32))
+    assert np.array_equal(rgb, orgb)
+    assert st["rays"] == octr["rays"]
 
 
 @pytest.mark.gpu
