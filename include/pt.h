@@ -269,7 +269,8 @@ int pt_abi_version(void);
 
 /* ------------------------------------------------------------ test hooks
  * Host execution of the device traversal code (pt_trace.h) for CPU unit
- * tests of the stack-DFS logic.  Never used by pt_render. */
+ * tests of the stack-DFS logic, and the device code's scalar functions one by
+ * one (pt_selftest_math).  Never used by pt_render. */
 int pt_selftest_ray_intersection(pt_scene* s, int32_t traversal, uint32_t n, const float* rays, int32_t* ids,
                                  float* hits, uint64_t* counters8);
 int pt_selftest_render_host(pt_scene* s, int32_t traversal, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
@@ -283,6 +284,23 @@ int pt_selftest_gamma_table(const pt_scene* s, float* thr256);
  * aux_stack_words (the scene's wide aux traversal stack, which a carry record holds).
  * Prepares the scene if needed. */
 int pt_selftest_wave_plan(pt_scene* s, const pt_session_opts* o, uint32_t cus, char* buf, size_t cap);
+/* The scalar building blocks of the device code (logf, the RNG streams, the normal and cosine
+ * samplers, the Schlick term, the resolve's mean + tonemap + 8-bit step, IEEE divide / sqrt /
+ * conversions), element by element: n records in, n records out (little-endian, packed).
+ * device >= 0: one element per thread in a kernel of their own on that device; device < 0: the
+ * same inline functions compiled for the host (needs no GPU).
+ *   op        record in                          record out
+ *   LOGF      f32 x                              f32 logf(x)
+ *   RNG       u32 seed, u32 n (one n per call)   n uniform, n normal, n mixed draws (f32; 3 fresh streams)
+ *   NORMAL3   u32 seed, u32 pre                  8 x 3 f32: consecutive unit normal vectors
+ *   COSINE    u32 seed, u32 pre, 3 f32 normal    8 x 3 f32: consecutive cosine samples about it
+ *   FRESNEL   f32 eta1, eta2, cosn               f32 reflection probability, -1 = total internal reflection
+ *   RESOLVE   f32 sum, u32 samples               f32 mean, u32 8-bit value
+ *   ARITH     f32 a, b, f64 a, b                 f32 a/b, sqrtf(|a|), f64 a/b, sqrt(|a|), f32 (float)a64, (float)(double)a
+ * pre = normal draws made on the stream first (odd: the sampler starts with a saved value). */
+enum { PT_MATH_LOGF = 0, PT_MATH_RNG = 1, PT_MATH_NORMAL3 = 2, PT_MATH_COSINE = 3, PT_MATH_FRESNEL = 4,
+       PT_MATH_RESOLVE = 5, PT_MATH_ARITH = 6 };
+int pt_selftest_math(int device, uint32_t op, uint64_t n, const void* in, void* out);
 
 #ifdef __cplusplus
 }

@@ -72,6 +72,7 @@ const float kPI = (float)std::acos(-1.0);    // include/distributions.h:14
 // libstdc++ (GCC 11): minstd_rand (random.tcc:116-124), generate_canonical<float,24>
 // (random.tcc:3348-3378), normal_distribution<float> Marsaglia polar with cache
 // (random.tcc:1802-1835).  Bundle mirrors RANDOM_t (include/distributions.h:16-20).
+inline float log_f(float x) { return std::log(x); }   // libm logf, as normal_distribution<float> calls it
 struct Rng {
     uint32_t x;
     float saved;
@@ -98,7 +99,7 @@ struct Rng {
             y1 = (float)(2.0f * uniform() - 1.0);
             r2 = x1 * x1 + y1 * y1;
         } while (r2 > 1.0 || r2 == 0.0);
-        const float mult = std::sqrt(-2 * std::log(r2) / r2);
+        const float mult = std::sqrt(-2 * log_f(r2) / r2);
         saved = x1 * mult;
         saved_ok = true;
         return y1 * mult * 1.0f + 0.0f;
@@ -685,6 +686,16 @@ inline void tally(uint64_t* cen, int id, CenEvent e, bool interior) {
     if (cen) ++cen[(size_t)id * CEN_CELLS + 2 * e + (interior ? 1 : 0)];
 }
 
+// src/scene.cpp:141-151: the refraction sine (always) and, unless |sin2| > 1 (total internal
+// reflection: false), Schlick's reflection probability
+inline bool fresnel_rr(float eta1, float eta2, float cosn, float& sin2, float& rr) {
+    sin2 = (float)((double)(eta1 / eta2) * std::sqrt((double)smax(0.f, 1 - cosn * cosn)));
+    if (std::fabs((double)sin2) > 1.) return false;
+    const float r0 = (float)std::pow((double)((eta1 - eta2) / (eta1 + eta2)), 2.);
+    rr = (float)((double)r0 + (double)(1 - r0) * std::pow((double)(1 - cosn), 5.));
+    return true;
+}
+
 // src/scene.cpp:83-178 (recursive, like the reference)
 V3 ray_trace(const Scene& S, Rng& R, const Ray& ray, unsigned depth, uint64_t* loc, uint64_t* cen) {
     if (depth == 0) return V3{0.f, 0.f, 0.f};
@@ -721,15 +732,13 @@ V3 ray_trace(const Scene& S, Rng& R, const Ray& ray, unsigned depth, uint64_t* l
             if (interior) std::swap(eta1, eta2);
             const V3 dir = -1.f * fnormalize(ray.d);
             const float cosn = fdot(normal, dir);
-            const float sin2 = (float)((double)(eta1 / eta2) * std::sqrt((double)smax(0.f, 1 - cosn * cosn)));
-            if (std::fabs((double)sin2) > 1.) {
+            float sin2, rr;
+            if (!fresnel_rr(eta1, eta2, cosn, sin2, rr)) {
                 tally(cen, rh.id, CEN_TIR, interior);
                 const V3 rd = reflect(normal, fnormalize(ray.d));
                 other = ray_trace(S, R, Ray{p + eps * rd, rd}, depth - 1, loc, cen);
                 break;
             }
-            const float r0 = (float)std::pow((double)((eta1 - eta2) / (eta1 + eta2)), 2.);
-            const float rr = (float)((double)r0 + (double)(1 - r0) * std::pow((double)(1 - cosn), 5.));
             if (R.uniform() < rr) {
                 tally(cen, rh.id, CEN_FRESNEL, interior);
                 const V3 rd = reflect(normal, fnormalize(ray.d));
@@ -938,6 +947,69 @@ int oracle_rng(uint32_t seed, uint32_t n, float* out) {
         }
     }
     return 0;
+}
+
+// ---- the integrator's scalar building blocks, element by element (each entry point calls the
+// function ray_trace / sample_pixel use, so the image fixtures pin it)
+void oracle_logf(uint64_t n, const float* x, float* out) {
+    for (uint64_t i = 0; i < n; ++i) out[i] = log_f(x[i]);
+}
+
+// mismatches (as bit patterns) between got[i] and logf(x[i]); up to 16 threads
+uint64_t oracle_logf_mismatches(uint64_t n, const float* x, const float* got) {
+    const int nt = std::max(1, std::min(16, (int)std::thread::hardware_concurrency()));
+    std::atomic<uint64_t> bad{0};
+    std::vector<std::thread> th;
+    for (int t = 0; t < nt; ++t) {
+        th.emplace_back([&, t]() {
+            uint64_t b = 0;
+            for (uint64_t i = n * t / nt; i < n * (t + 1) / nt; ++i) {
+                const float r = log_f(x[i]);
+                if (std::memcmp(&r, &got[i], 4) != 0) ++b;
+            }
+            bad += b;
+        });
+    }
+    for (auto& v : th) v.join();
+    return bad;
+}
+
+// in: n x {eta1, eta2, cosn}; out: n x rr, or -1 for total internal reflection
+void oracle_fresnel(uint64_t n, const float* in, float* out) {
+    for (uint64_t i = 0; i < n; ++i) {
+        float sin2, rr;
+        out[i] = fresnel_rr(in[3 * i], in[3 * i + 1], in[3 * i + 2], sin2, rr) ? rr : -1.f;
+    }
+}
+
+// in: n x {u32 seed, u32 pre}: a fresh stream, `pre` normal draws, then 8 normal01_vec -> out: n x 8 x 3 f32
+void oracle_normal_vecs(uint64_t n, const uint32_t* in, float* out) {
+    for (uint64_t i = 0; i < n; ++i) {
+        Rng R(in[2 * i]);
+        for (uint32_t k = 0; k < in[2 * i + 1]; ++k) (void)R.normal();
+        for (int k = 0; k < 8; ++k) {
+            const V3 v = normal01_vec(R);
+            float* o = out + (i * 8 + k) * 3;
+            o[0] = v.x; o[1] = v.y; o[2] = v.z;
+        }
+    }
+}
+
+// in: n x {u32 seed, u32 pre, 3 f32 normal} (20 B): the same stream, 8 sample_cosine about the normal
+void oracle_sample_cosine(uint64_t n, const void* in, float* out) {
+    for (uint64_t i = 0; i < n; ++i) {
+        uint32_t sp[2];
+        float nn[3];
+        std::memcpy(sp, static_cast<const unsigned char*>(in) + 20 * i, 8);
+        std::memcpy(nn, static_cast<const unsigned char*>(in) + 20 * i + 8, 12);
+        Rng R(sp[0]);
+        for (uint32_t k = 0; k < sp[1]; ++k) (void)R.normal();
+        for (int k = 0; k < 8; ++k) {
+            const V3 v = sample_cosine(R, V3{nn[0], nn[1], nn[2]});
+            float* o = out + (i * 8 + k) * 3;
+            o[0] = v.x; o[1] = v.y; o[2] = v.z;
+        }
+    }
 }
 
 void oracle_tonemap(uint32_t n, const float* rad, uint8_t* rgb) {

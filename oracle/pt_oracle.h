@@ -22,6 +22,12 @@ int oracle_render_census(oracle_scene* o, uint32_t x0, uint32_t y0, uint32_t w, 
 int oracle_prim_info(const oracle_scene* o, uint32_t* out);
 int oracle_ray_intersection(const oracle_scene* o, uint32_t n, const float* rays, int32_t* ids, float* hit);
 int oracle_rng(uint32_t seed, uint32_t n, float* out);
+/* the integrator's scalar building blocks, element by element (see pt_oracle.cpp) */
+void oracle_logf(uint64_t n, const float* x, float* out);
+uint64_t oracle_logf_mismatches(uint64_t n, const float* x, const float* got);
+void oracle_fresnel(uint64_t n, const float* in, float* out);
+void oracle_normal_vecs(uint64_t n, const uint32_t* in, float* out);
+void oracle_sample_cosine(uint64_t n, const void* in, float* out);
 void oracle_tonemap(uint32_t n, const float* rad, uint8_t* rgb);
 void oracle_gamma_u8(uint32_t n, const float* v, uint8_t* out);
 uint64_t oracle_check_gamma_table(const float* thr);

@@ -73,7 +73,8 @@ PT_HD float u2f(uint32_t u) { union { float f; uint32_t u; } c; c.u = u; return 
 // the function libstdc++'s std::log(float) calls in the reference's
 // normal_distribution.  Restated so the device matches it exactly; pinned by
 // an exhaustive comparison against the host libm over every float in (0, 1]
-// (the only range the polar method feeds it).
+// (the only range the polar method feeds it):
+// tests/test_math_host.py::test_logf_exhaustive (slow test).
 struct LogfEntry { double invc, logc; };
 // table in constant memory on the device (a dynamically indexed local array
 // would be materialised in 32 VGPRs)
@@ -591,6 +592,18 @@ PT_HD uint32_t quantize_gamma(float v, const float* thr) {
     for (uint32_t step = 128; step >= 1; step >>= 1)
         if (thr[lo + step - 1] <= v) lo += step;
     return lo;
+}
+// src/scene.cpp:201: a pixel's mean, (1.f / SAMPLES) * sum -- a product with the rounded
+// reciprocal, not sum / SAMPLES (the two differ whenever SAMPLES is no power of two)
+PT_HD float sample_mean(float sum, uint32_t samples) {
+    const float inv = 1.f / (float)samples;
+    return inv * sum;
+}
+// one channel of the resolve: the mean and its 8-bit value (k_resolve, and the RESOLVE
+// op of pt_selftest_math)
+PT_HD uint32_t resolve_channel(float sum, uint32_t samples, const float* thr, float& mean) {
+    mean = sample_mean(sum, samples);
+    return quantize_gamma(aces1(mean), thr);
 }
 
 }  // namespace pt

@@ -98,12 +98,12 @@ __global__ void __launch_bounds__(256) k_resolve(ResolveParams P) {
     uint32_t px, py;
     const bool pix = slot_pixel(P.tm, blockIdx.x, threadIdx.x, px, py);
     wave_add_u64(ctr_copy(P.counters) + CTR_SHORT, pix && load_hot(P.st, slot).done != P.samples ? 1ull : 0ull);
-    const float inv = 1.f / (float)P.samples;    // src/scene.cpp:201: (1.f / SAMPLES) * sum
     const f3 s = load_sum(P.st, slot);
-    const float m[3] = {inv * s.x, inv * s.y, inv * s.z};
+    const float sum[3] = {s.x, s.y, s.z};
+    float m[3];
     uint8_t* o = P.out + (size_t)slot * 3u;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) o[c] = (uint8_t)quantize_gamma(aces1(m[c]), thr);
+    for (int c = 0; c < 3; ++c) o[c] = (uint8_t)resolve_channel(sum[c], P.samples, thr, m[c]);
     if (P.rad) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) P.rad[(size_t)slot * 3u + c] = m[c];

@@ -465,6 +465,17 @@ PT_HD int ray_intersection(const SceneView& S, const ReplayCfg& cfg, const Ray& 
 // per-vertex fold record modes
 enum : uint32_t { V_TERM = 0u, V_DIFFUSE = 1u, V_COL = 2u, V_IDENT = 3u };
 
+// src/scene.cpp:141-151: the dielectric's refraction sine sin2 (in every case) and, unless
+// |sin2| > 1 (total internal reflection: returns false), Schlick's reflection probability rr
+PT_HD bool fresnel_schlick(float eta1, float eta2, float cosn, float& sin2, float& rr) {
+    sin2 = (float)((double)(eta1 / eta2) * sqrt((double)smax(0.f, 1.f - cosn * cosn)));
+    if (fabs((double)sin2) > 1.0) return false;
+    const float q = (eta1 - eta2) / (eta1 + eta2);
+    const float r0 = (float)((double)q * (double)q);             // pow(q, 2.)
+    rr = (float)((double)r0 + (double)(1.f - r0) * pow5_cr((double)(1.f - cosn)));
+    return true;
+}
+
 // One path vertex of RayTrace (src/scene.cpp:91-177) after a closest hit:
 // consumes the vertex's random numbers, returns its fold record
 // (idm = prim id | mode << 30, factors s1, s2) and whether the path continues
@@ -505,16 +516,9 @@ PT_HD bool shade_vertex_e(const SceneView& S, const EM& em, const Shade& sh, Rng
         if (h.interior) { const float tt = eta1; eta1 = eta2; eta2 = tt; }
         const f3 dir = -1.f * normalize(ray.d);
         const float cosn = dot(n, dir);
-        const float sin2 = (float)((double)(eta1 / eta2) * sqrt((double)smax(0.f, 1.f - cosn * cosn)));
-        bool refl;
-        if (fabs((double)sin2) > 1.0) {
-            refl = true;                                  // total internal reflection
-        } else {
-            const float q = (eta1 - eta2) / (eta1 + eta2);
-            const float r0 = (float)((double)q * (double)q);             // pow(q, 2.)
-            const float rr = (float)((double)r0 + (double)(1.f - r0) * pow5_cr((double)(1.f - cosn)));
-            refl = rng_uniform(R) < rr;
-        }
+        float sin2, rr;
+        bool refl = true;                                 // total internal reflection
+        if (fresnel_schlick(eta1, eta2, cosn, sin2, rr)) refl = rng_uniform(R) < rr;
         s1 = s2 = 1.f;
         if (refl) {
             const f3 rd = reflect(n, normalize(ray.d));

@@ -10,7 +10,8 @@
 //   rounds.cpp    the wavefront pass: path rounds, early / final cooperative launches
 //   render.cpp    Scene::Render equivalent: per-GPU threads, the RCCL / host gather, PPM
 //   rayq.cpp      the ray-query engine: closest-hit queries for the caller's rays (pt_rayq_*, pt_intersect)
-//   selftest.cpp  host execution of the device query / integrator code (tests only; the fourth
+//   selftest.cpp  host execution of the device query / integrator code, and pt_selftest_math (the
+//                 device code's scalar functions on the host or in k_selftest_math) (tests only; one
 //                 hook, pt_selftest_wave_plan, is in session.cpp beside the set-up it reports)
 #pragma once
 #include "pt.h"

@@ -1,10 +1,12 @@
 // selftest.cpp -- host execution of the device query and integrator code (pt_query.h,
-// pt_coop.h, pt_trace.h) for the CPU tests; never used by pt_render.
+// pt_coop.h, pt_trace.h) for the CPU tests, and pt_selftest_math: the device code's scalar
+// functions element by element, on the host or on a device (pt_selftest.h); never used by pt_render.
 #include <stdio.h>
 #include <string.h>
 
 #include <array>
 #include "api_internal.h"
+#include "../device/pt_selftest.h"
 
 namespace pti {
 namespace {
@@ -130,8 +132,9 @@ int pt_selftest_render_host(pt_scene* s, int32_t traversal, uint32_t x0, uint32_
                         sum = sum + pt::trace_path<false>(V, cfg, ray, s->hs.depth, R, stk, vs, C);
                     }
                 }
-                const pt::f3 m = (1.f / (float)S) * sum;
-                radiance[3 * k] = m.x; radiance[3 * k + 1] = m.y; radiance[3 * k + 2] = m.z;
+                radiance[3 * k] = pt::sample_mean(sum.x, S);
+                radiance[3 * k + 1] = pt::sample_mean(sum.y, S);
+                radiance[3 * k + 2] = pt::sample_mean(sum.z, S);
             }
             errs[t] = C.errs;
         });
@@ -150,6 +153,52 @@ int pt_selftest_render_host(pt_scene* s, int32_t traversal, uint32_t x0, uint32_
 int pt_selftest_gamma_table(const pt_scene* s, float* thr256) {
     if (!s || !s->prepared || !thr256) return fail(PT_E_INVALID, "scene not prepared");
     memcpy(thr256, s->thr, sizeof(s->thr));
+    return PT_OK;
+}
+
+static_assert(pt::MATH_LOGF == PT_MATH_LOGF && pt::MATH_RNG == PT_MATH_RNG && pt::MATH_NORMAL3 == PT_MATH_NORMAL3 &&
+                  pt::MATH_COSINE == PT_MATH_COSINE && pt::MATH_FRESNEL == PT_MATH_FRESNEL &&
+                  pt::MATH_RESOLVE == PT_MATH_RESOLVE && pt::MATH_ARITH == PT_MATH_ARITH && pt::MATH_N == 7u,
+              "math ops: device and ABI numbering differ");
+
+int pt_selftest_math(int device, uint32_t op, uint64_t n, const void* in, void* out) {
+    if (op >= pt::MATH_N) return fail(PT_E_INVALID, "unknown math op");
+    if (n == 0) return PT_OK;
+    if (!in || !out) return fail(PT_E_INVALID, "null argument");
+    if (n > (1ull << 26)) return fail(PT_E_INVALID, "more than 2^26 elements");
+    // RNG: one output length for the whole call, the first element's
+    uint32_t rng_n = 0;
+    if (op == pt::MATH_RNG) {
+        const pt::MathSeedIn* I = static_cast<const pt::MathSeedIn*>(in);
+        rng_n = I[0].pre;
+        if (rng_n == 0 || rng_n > 65536u) return fail(PT_E_INVALID, "RNG: 1 .. 65536 draws per stream");
+        for (uint64_t i = 1; i < n; ++i)
+            if (I[i].pre != rng_n) return fail(PT_E_INVALID, "RNG: every element asks for the same number of draws");
+    }
+    const size_t in_bytes = (size_t)n * pt::math_in_bytes(op), out_bytes = (size_t)n * pt::math_out_bytes(op, rng_n);
+    if (in_bytes > (1ull << 31) || out_bytes > (1ull << 31)) return fail(PT_E_INVALID, "more than 2 GiB of records");
+    float thr[256] = {0.f};
+    if (op == pt::MATH_RESOLVE) pth::build_gamma_thresholds(thr);
+    if (device < 0) {
+        parallel_chunks((size_t)n, std::min(16u, std::max(1u, std::thread::hardware_concurrency())),
+                        [&](size_t b, size_t e, unsigned) {
+                            for (size_t i = b; i < e; ++i) pt::math_one(op, i, in, out, thr, rng_n);
+                        });
+        return PT_OK;
+    }
+    if (const int rc = check_device(device)) return rc;
+    HIP_TRY(hipSetDevice(device));
+    unsigned char* buf = nullptr;   // in | out | thr, each 256-B aligned
+    const size_t o_out = (in_bytes + 255u) & ~(size_t)255u, o_thr = o_out + ((out_bytes + 255u) & ~(size_t)255u);
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf), o_thr + sizeof(thr)));
+    hipError_t e = hipMemcpy(buf, in, in_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(buf + o_thr, thr, sizeof(thr), hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = pt_launch_selftest_math(op, n, buf, buf + o_out, reinterpret_cast<const float*>(buf + o_thr), rng_n, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, buf + o_out, out_bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(buf);
+    if (e != hipSuccess) return fail(PT_E_HIP, std::string("pt_selftest_math: ") + hipGetErrorString(e));
     return PT_OK;
 }
 

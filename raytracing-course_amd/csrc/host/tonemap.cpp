@@ -8,7 +8,7 @@
 // a saturated channel value to (number of thresholds <= v), which equals the
 // reference's byte whenever the host map is monotone in v -- checked
 // exhaustively over all 1,065,353,217 floats in [0, 1] by
-// tests/test_host.py::test_gamma_table_monotone (slow test).
+// tests/test_host.py::test_gamma_table_exhaustive (slow test).
 #include <math.h>
 #include <stdint.h>
 #include <string.h>

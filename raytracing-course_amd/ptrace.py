@@ -35,6 +35,20 @@ ABI_VERSION = 6
 # a ray query's hit record (pt_ray_hit, 24 B); a miss is id = -1 with the other fields 0
 HIT_DTYPE = np.dtype([("id", np.int32), ("t", np.float32), ("n", np.float32, (3,)), ("interior", np.uint32)])
 RAYS_CHUNK = 1 << 22   # pt_intersect moves the rays in chunks of at most this many
+# pt_selftest_math's ops (include/pt.h PT_MATH_*): name -> (op, record in, record out; None = 3n f32)
+_VECS = np.dtype([("v", np.float32, (8, 3))])
+MATH_OPS = {
+    "LOGF": (0, np.dtype(np.float32), np.dtype(np.float32)),
+    "RNG": (1, np.dtype([("seed", np.uint32), ("n", np.uint32)]), None),
+    "NORMAL3": (2, np.dtype([("seed", np.uint32), ("pre", np.uint32)]), _VECS),
+    "COSINE": (3, np.dtype([("seed", np.uint32), ("pre", np.uint32), ("n", np.float32, (3,))]), _VECS),
+    "FRESNEL": (4, np.dtype([("eta1", np.float32), ("eta2", np.float32), ("cosn", np.float32)]), np.dtype(np.float32)),
+    "RESOLVE": (5, np.dtype([("sum", np.float32), ("samples", np.uint32)]),
+                np.dtype([("mean", np.float32), ("byte", np.uint32)])),
+    "ARITH": (6, np.dtype([("a", np.float32), ("b", np.float32), ("ad", np.float64), ("bd", np.float64)]),
+              np.dtype([("quot", np.float32), ("root", np.float32), ("quotd", np.float64), ("rootd", np.float64),
+                        ("narrow", np.float32), ("round_trip", np.float32)])),
+}
 
 # One HIP runtime per process: PyTorch bundles its own libamdhip64 (soname
 # libamdhip64.so.7, but its users link the unversioned name), so loading
@@ -127,6 +141,7 @@ _sig = {
                                           C.c_uint32, _P]),
     "pt_selftest_gamma_table": (C.c_int, [_P, _P]),
     "pt_selftest_wave_plan": (C.c_int, [_P, C.POINTER(SessionOpts), C.c_uint32, C.c_char_p, C.c_size_t]),
+    "pt_selftest_math": (C.c_int, [C.c_int, C.c_uint32, C.c_uint64, _P, _P]),
 }
 for _name, (_res, _args) in _sig.items():
     _f = getattr(_lib, _name)
@@ -407,6 +422,21 @@ def write_ppm(path, rgb):
     rgb = np.ascontiguousarray(rgb, np.uint8)
     h, w, _ = rgb.shape
     _check(_lib.pt_write_ppm(os.fsencode(path), w, h, _ptr(rgb)))
+
+
+def selftest_math(op, records, device=-1):
+    """pt_selftest_math: `records` (an array of MATH_OPS[op]'s input dtype) through the device
+    code's scalar functions, on `device` or (device < 0) compiled for the host.  Returns an
+    array of the op's output dtype; RNG returns float32 of shape (len(records), 3 * n)."""
+    code, din, dout = MATH_OPS[op]
+    records = np.ascontiguousarray(records, din).reshape(-1)
+    if dout is None:
+        n = int(records["n"][0]) if len(records) else 0
+        out = np.zeros((len(records), 3 * n), np.float32)
+    else:
+        out = np.zeros(len(records), dout)
+    _check(_lib.pt_selftest_math(device, code, len(records), _ptr(records), _ptr(out)))
+    return out
 
 
 def abi_version():

@@ -52,6 +52,11 @@ def oracle():
         lib.oracle_ray_intersection.argtypes = [P, C.c_uint32, P, P, P]
         lib.oracle_rng.argtypes = [C.c_uint32, C.c_uint32, P]
         lib.oracle_tonemap.argtypes = [C.c_uint32, P, P]
+        for name in ("oracle_logf", "oracle_fresnel", "oracle_normal_vecs", "oracle_sample_cosine"):
+            getattr(lib, name).argtypes = [C.c_uint64, P, P]
+            getattr(lib, name).restype = None
+        lib.oracle_logf_mismatches.argtypes = [C.c_uint64, P, P]
+        lib.oracle_logf_mismatches.restype = C.c_uint64
         lib.oracle_gamma_u8.argtypes = [C.c_uint32, P, P]
         lib.oracle_check_gamma_table.argtypes = [P]
         lib.oracle_check_gamma_table.restype = C.c_uint64

@@ -56,6 +56,12 @@ IMAGES = {
     "hw3s5_48x48x8": ("hw3_sample5.txt", (48, 48, 8, False, "diffuse"), None),
     "hw3s6_48x48x8": ("hw3_sample6.txt", (48, 48, 8, False, "diffuse"), None),
     "rabbid_48x48x4": ("rabbid_sample.txt", (48, 48, 4, False, "diffuse"), None),
+    # SAMPLES that are no power of two: the mean is (1.f / SAMPLES) * sum, and only then does the
+    # rounded reciprocal differ from a division (every other fixture's 1 / SAMPLES is exact);
+    # sizes off the 16-pixel tile grid in one direction each
+    "p51_40x24x3": ("practice5_1.txt", (40, 24, 3, False, "diffuse"), None),
+    "dragon_glass_40x24x7": ("practice5_dragon_10k.txt", (40, 24, 7, False, "glass"), None),
+    "hw3s4_24x40x5": ("hw3_sample4.txt", (24, 40, 5, False, "diffuse"), None),
     # windows of the benchmark configurations (global-index seeds kept)
     "c2_win_240_200_24x24": ("c2", None, (240, 200, 24, 24)),
     "c3s4_win_944_520_16x16": ("c3", (1920, 1080, 4, True, "diffuse"), (944, 520, 16, 16)),
@@ -160,8 +166,27 @@ def render_image(harness, tmp, name, table=None):
         cli_ppm = os.path.join(tmp, name + "_cli.ppm")
         subprocess.check_call([os.path.join(REF, "raytracing_hw5"), sc, cli_ppm], stdout=subprocess.DEVNULL)
         assert md5f(cli_ppm) == entry["ppm_md5"], name
+    if table is None:
+        restatement_counters(name, IMAGES)
     print("image", name, entry["ppm_md5"])
     return entry
+
+
+def restatement_counters(name, table):
+    """The CPU restatement (oracle/pt_oracle.cpp) must give the fixture just recorded, image and
+    radiance, byte for byte; returns its counters."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import _util as U
+    src, gen, win = table[name]
+    o = U.OracleScene(U.scene_path(src, tuple(gen) if gen else None))
+    x0, y0, w, h = win if win else (0, 0, None, None)
+    rgb, rad, ctr = o.render(x0, y0, w, h)
+    ref_rad = np.fromfile(os.path.join(HERE, "rad_%s.f32" % name), np.float32).reshape(rad.shape)
+    ref_img = U.read_ppm(os.path.join(HERE, "img_%s.ppm" % name))
+    assert np.array_equal(rad.view(np.uint32), ref_rad.view(np.uint32)), name + ": restatement radiance differs"
+    assert np.array_equal(rgb, ref_img), name + ": restatement image differs"
+    return ctr
 
 
 def record_rays(harness, tmp, name):
@@ -181,19 +206,8 @@ def record_rays(harness, tmp, name):
 
 def render_deep(harness, tmp, name):
     """A DEEP fixture: the reference's window + the restatement's ray count."""
-    import numpy as np
-    sys.path.insert(0, os.path.join(REPO, "tests"))
-    import _util as U
     entry = render_image(harness, tmp, name, DEEP)
-    src, gen, win = DEEP[name]
-    sc = scene_file(tmp, src, gen)
-    o = U.OracleScene(sc)
-    x0, y0, w, h = win if win else (0, 0, None, None)
-    rgb, rad, ctr = o.render(x0, y0, w, h)
-    ref_rad = np.fromfile(os.path.join(HERE, "rad_%s.f32" % name), np.float32).reshape(rad.shape)
-    ref_img = U.read_ppm(os.path.join(HERE, "img_%s.ppm" % name))
-    assert np.array_equal(rad.view(np.uint32), ref_rad.view(np.uint32)), name + ": restatement radiance differs"
-    assert np.array_equal(rgb, ref_img), name + ": restatement image differs"
+    ctr = restatement_counters(name, DEEP)
     entry["rays"] = int(ctr["rays"])
     print("deep", name, entry["rays"], "rays")
     return entry

@@ -202,7 +202,9 @@ def test_traversal_matches_reference_kat(name, trav):
 HOST_RENDER = ["p51_64x48x16", "p52_64x48x16", "dragon_metal_64x64x8", "dragon_glass_64x64x8",
                "hw3s2_48x48x8", "hw3s3_48x48x8",
                "mat_matrix_24x24x8", "mat_inside_24x24x8", "mat_camera_23x17x8",   # _material_scenes.py
-               "hw3s4_48x48x8", "hw3s5_48x48x8", "rabbid_48x48x4", "c2_win_240_200_24x24"]
+               "hw3s4_48x48x8", "hw3s5_48x48x8", "rabbid_48x48x4", "c2_win_240_200_24x24",
+               # SAMPLES 3, 7 and 5: the mean's 1 / SAMPLES is rounded (make_golden.py)
+               "p51_40x24x3", "dragon_glass_40x24x7", "hw3s4_24x40x5"]
 
 
 # every traversal on every fixture; on the first nine also the megakernel's query with the
@@ -224,6 +226,20 @@ def test_device_integrator_on_host_bit_exact(name, trav, monkeypatch):
         got = s.selftest_render_host(x0, y0, w, h, traversal=TRAVERSALS.get(trav, 0))
     assert got.view(np.uint32).tolist() == rad.view(np.uint32).tolist()
     assert np.array_equal(U.oracle_tonemap(got).reshape(img.shape), img)
+
+
+@pytest.mark.parametrize("trav", sorted(TRAVERSALS))
+@pytest.mark.parametrize("spp", [3, 7])
+def test_host_render_odd_sample_counts_vs_oracle(spp, trav):
+    """The host render's mean (selftest.cpp) is the device's rule, pt_core.h sample_mean =
+    (1.f / S) * sum: at S = 3 and 7, where 1 / S is rounded and a division would differ, on the
+    scene of tests/test_samples.py (its CPU twin)."""
+    p = U.scene_path("practice5_dragon_10k.txt", (40, 24, 7, False, "diffuse"))
+    _, orad, _ = U.OracleScene(p).render(spp=spp)
+    with pt.Scene.load(p) as s:
+        s.prepare()
+        got = s.selftest_render_host(0, 0, 40, 24, spp=spp, traversal=TRAVERSALS[trav])
+    assert got.view(np.uint32).tolist() == orad.view(np.uint32).tolist()
 
 
 @pytest.mark.parametrize("name", sorted(M["trav"]))
