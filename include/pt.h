@@ -264,6 +264,41 @@ void pt_rayq_free(pt_rayq* q);
  * device memory stays bounded; synchronous; stats may be NULL */
 int pt_intersect(pt_scene* s, int device, uint64_t n, const pt_ray* rays, pt_ray_hit* hits, pt_stats* stats);
 
+/* ------------------------------------------------------------ batch radiance
+ * Scene::RayTrace (src/scene.cpp:83-178) for the caller's own rays, bit for bit (additions to
+ * ABI 6: no existing struct or function changed).  No reference counterpart as an interface:
+ * RayTrace is private to the reference's render, reachable only through the scene's one pinhole
+ * camera.  One record is one call: its output is RayTrace(random, Ray{o, d}, RAY_DEPTH) with
+ * `random` a fresh std::minstd_rand rnd(seed) and fresh uniform / normal distributions.
+ * RAY_DEPTH is the scene's value when the context is created (pt_scene_override applies).  The
+ * ray is used as given (never normalised; a non-finite ray is answered as the reference answers
+ * it).  rgb is the value RayTrace returns, not a mean; rays = the path's RayIntersection calls
+ * (0 when RAY_DEPTH is 0).  `reserved` is written as 0 and not read.  A caller who wants many
+ * samples sends many records, with their own jitter and seeds. */
+typedef struct pt_pathq pt_pathq;
+typedef struct pt_path_ray  { float o[3], d[3]; uint32_t seed; uint32_t reserved; } pt_path_ray;   /* 32 B */
+typedef struct pt_path_out  { float rgb[3]; uint32_t rays; } pt_path_out;                          /* 16 B */
+
+/* a batch radiance context on `device` for runs of up to max_paths (1 .. 2^32 - 1) paths; prepares
+ * the scene if needed; the scene must outlive the context.  The context holds RAY_DEPTH x 16 B of
+ * device memory per resident lane (PT_E_OOM if one wave per compute unit would pass 1 GiB). */
+int pt_pathq_create(pt_scene* s, int device, uint64_t max_paths, pt_pathq** out);
+/* asynchronous on `stream` (a hipStream_t; NULL = the null stream); dev_in / dev_out are 16-byte
+ * aligned device pointers on the context's device; n <= max_paths; n = 0 enqueues nothing.  One
+ * run at a time per context: a run first waits (on the host) for the context's previous run. */
+int pt_pathq_run(pt_pathq* q, void* stream, uint64_t n, const pt_path_ray* dev_in, pt_path_out* dev_out);
+/* waits for the last run; fills rays, node_visits, prim_tests, plane_tests, aux_visits, fallbacks,
+ * fallbacks_ray (over every vertex of every path), errors (must be 0), kernel_ms and the *_bytes
+ * record sizes for the runs since the last call */
+int pt_pathq_stats(pt_pathq* q, pt_stats* st);
+void pt_pathq_free(pt_pathq* q);
+/* convenience, host pointers: uploads, runs, downloads, in chunks of at most 2^22 paths so that
+ * device memory stays bounded; synchronous; stats may be NULL */
+int pt_radiance(pt_scene* s, int device, uint64_t n, const pt_path_ray* in, pt_path_out* out, pt_stats* stats);
+/* Camera::GetToRay(x, y) (src/scene.cpp:180-187) for n float pixel coordinates xy[2i], xy[2i + 1]:
+ * the ray a pixel sample at (x, y) starts with (the direction is not normalised).  Host only. */
+int pt_camera_rays(pt_scene* s, uint64_t n, const float* xy, pt_ray* out);
+
 const char* pt_last_error(void);
 int pt_abi_version(void);
 
@@ -275,6 +310,11 @@ int pt_selftest_ray_intersection(pt_scene* s, int32_t traversal, uint32_t n, con
                                  float* hits, uint64_t* counters8);
 int pt_selftest_render_host(pt_scene* s, int32_t traversal, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                             uint32_t spp, float* radiance);
+/* n batch radiance records on the host: trace_path_with over the query state machine run to
+ * completion, as pt_selftest_render_host runs a pixel's samples.  Fills out (rgb, and each path's
+ * rays) and counters8: the totals of rays, nodes, primitive tests, plane tests, errors, aux
+ * visits, fallbacks and non-finite-ray fallbacks (the CTR_* slots).  counters8 may be NULL. */
+int pt_selftest_paths_host(pt_scene* s, uint64_t n, const pt_path_ray* in, pt_path_out* out, uint64_t* counters8);
 /* the 256-entry gamma threshold table used by the device tonemap */
 int pt_selftest_gamma_table(const pt_scene* s, float* thr256);
 /* session set-up without a device: the geometry (o's rank, world, window, traversal; o->device is

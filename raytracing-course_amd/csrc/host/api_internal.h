@@ -10,6 +10,8 @@
 //   rounds.cpp    the wavefront pass: path rounds, early / final cooperative launches
 //   render.cpp    Scene::Render equivalent: per-GPU threads, the RCCL / host gather, PPM
 //   rayq.cpp      the ray-query engine: closest-hit queries for the caller's rays (pt_rayq_*, pt_intersect)
+//   pathq.cpp     the batch radiance engine: RayTrace for the caller's rays (pt_pathq_*, pt_radiance,
+//                 pt_camera_rays)
 //   selftest.cpp  host execution of the device query / integrator code, and pt_selftest_math (the
 //                 device code's scalar functions on the host or in k_selftest_math) (tests only; one
 //                 hook, pt_selftest_wave_plan, is in session.cpp beside the set-up it reports)
@@ -34,6 +36,7 @@
 
 #include "../device/pt_coop.h"
 #include "../device/pt_kernels.h"
+#include "../device/pt_paths.h"
 #include "../device/pt_rays.h"
 #include "pt_scene.h"
 
@@ -321,6 +324,22 @@ struct pt_rayq {
     bool pending = false;           // ... whose time has not been added to kernel_ms yet
     double kernel_ms = 0.0;         // since the last pt_rayq_stats
     unsigned long long seen[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the counters at the last pt_rayq_stats
+};
+
+// A batch radiance context (pathq.cpp): the scene's copy on one device and the run state of k_paths.
+struct pt_pathq {
+    pt_scene* sc = nullptr;
+    int dev = 0;
+    uint64_t max_paths = 0;
+    pt::PathsParams p{};            // the view of the device copy and the arena's pieces (in, out, n, batch: per run)
+    // one allocation: the control block | the statistics counters | the resident lanes' fold records
+    unsigned char* arena = nullptr;
+    uint32_t block = 256, max_grid = 1;   // k_paths' workgroup (its lanes' stacks fit the LDS) and the resident
+                                          // grid, which the fold area is sized for
+    hipEvent_t e0 = nullptr, e1 = nullptr;   // around the last run's kernel
+    bool pending = false;           // ... whose time has not been added to kernel_ms yet
+    double kernel_ms = 0.0;         // since the last pt_pathq_stats
+    unsigned long long seen[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the counters at the last pt_pathq_stats
 };
 
 #pragma GCC visibility pop

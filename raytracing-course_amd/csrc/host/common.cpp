@@ -112,6 +112,8 @@ const Rccl& rccl() {
 //                     a query needing more takes the exact DFS)
 //   rays_service=N    ray queries (pt_rayq_create): a wave retires its finished lanes and refills once N
 //                     lanes wait (1..64; 1 = on every trip; default PT_RAYS_SERVICE)
+//   paths_service=N   batch radiance (pt_pathq_create): a wave runs its service step (vertices, folds,
+//                     new paths) once N lanes wait (1..64; 1 = on every trip; default PT_PATHS_SERVICE)
 //   roundlog=1|2|3    per-round kernel times / each round's chains, wall time and rays / and the
 //                     pixels' remaining samples, on stderr
 //   wgprof=FILE       per-workgroup timelines (-DPT_WPROF builds)

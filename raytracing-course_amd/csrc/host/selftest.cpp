@@ -150,6 +150,47 @@ int pt_selftest_render_host(pt_scene* s, int32_t traversal, uint32_t x0, uint32_
     return PT_OK;
 }
 
+int pt_selftest_paths_host(pt_scene* s, uint64_t n, const pt_path_ray* in, pt_path_out* out, uint64_t* counters8) {
+    if (!s) return fail(PT_E_INVALID, "null scene");
+    if (n > 0 && (!in || !out)) return fail(PT_E_INVALID, "null path or radiance buffer");
+    int rc = pt_scene_prepare(s);
+    if (rc) return rc;
+    const pt::SceneView V = host_view(s, PT_TRAVERSAL_REPLAY);
+    HostStack stk;
+    HostVStore vs;
+    pt::Counts C{};
+    uint64_t exact_ray = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        // the batch radiance engine's query (pt_query.h state machine), run to completion
+        auto q = [&](const pt::Ray& rr, pt::Hit& hh, pt::Counts& cc) {
+            pt::QCounts Q{};
+            uint32_t ex = 0;
+            const int id = pt::q_run(V, rr, stk, hh, Q, ex);
+            cc.fallbacks += ex;
+            const float w = pt::q_prep(V, rr).w;
+            if (w != w) exact_ray++;   // a non-finite ray (q_init_pre: Q_EXACT from the start)
+            if (Q.planes & 0x80000000u) cc.errs |= 4u;   // recomputed hit differs
+            cc.nodes += Q.nodes; cc.ptests += Q.ptests; cc.planes += Q.planes & 0x7fffffffu; cc.aux += Q.aux;
+            return id;
+        };
+        pt::Ray ray;
+        ray.o = pt::mk3(in[i].o[0], in[i].o[1], in[i].o[2]);
+        ray.d = pt::mk3(in[i].d[0], in[i].d[1], in[i].d[2]);
+        pt::Rng R = pt::rng_seed(in[i].seed);
+        const uint64_t rays0 = C.rays;
+        const pt::f3 L = pt::trace_path_with(V, q, ray, s->hs.depth, R, vs, C);
+        out[i] = pt_path_out{{L.x, L.y, L.z}, (uint32_t)(C.rays - rays0)};
+    }
+    if (counters8) {
+        uint64_t c[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // (slots CTR_RAYS .. CTR_FALLBACKS_RAY)
+        c[pt::CTR_RAYS] = C.rays; c[pt::CTR_NODES] = C.nodes; c[pt::CTR_PTESTS] = C.ptests; c[pt::CTR_PLANES] = C.planes;
+        c[pt::CTR_ERRORS] = C.errs; c[pt::CTR_AUX] = C.aux; c[pt::CTR_FALLBACKS] = C.fallbacks;
+        c[pt::CTR_FALLBACKS_RAY] = exact_ray;
+        memcpy(counters8, c, sizeof(c));
+    }
+    return C.errs ? fail(PT_E_INVALID, "recomputed closest hit differs from the query's") : PT_OK;
+}
+
 int pt_selftest_gamma_table(const pt_scene* s, float* thr256) {
     if (!s || !s->prepared || !thr256) return fail(PT_E_INVALID, "scene not prepared");
     memcpy(thr256, s->thr, sizeof(s->thr));

@@ -35,6 +35,10 @@ ABI_VERSION = 6
 # a ray query's hit record (pt_ray_hit, 24 B); a miss is id = -1 with the other fields 0
 HIT_DTYPE = np.dtype([("id", np.int32), ("t", np.float32), ("n", np.float32, (3,)), ("interior", np.uint32)])
 RAYS_CHUNK = 1 << 22   # pt_intersect moves the rays in chunks of at most this many
+# batch radiance records (pt_path_ray 32 B, pt_path_out 16 B): one record = one RayTrace call
+PATH_DTYPE = np.dtype([("o", np.float32, (3,)), ("d", np.float32, (3,)), ("seed", np.uint32), ("reserved", np.uint32)])
+RADIANCE_DTYPE = np.dtype([("rgb", np.float32, (3,)), ("rays", np.uint32)])
+PATHS_CHUNK = 1 << 22   # pt_radiance moves the paths in chunks of at most this many
 # pt_selftest_math's ops (include/pt.h PT_MATH_*): name -> (op, record in, record out; None = 3n f32)
 _VECS = np.dtype([("v", np.float32, (8, 3))])
 MATH_OPS = {
@@ -134,11 +138,18 @@ _sig = {
     "pt_rayq_stats": (C.c_int, [_P, C.POINTER(Stats)]),
     "pt_rayq_free": (None, [_P]),
     "pt_intersect": (C.c_int, [_P, C.c_int, C.c_uint64, _P, _P, C.POINTER(Stats)]),
+    "pt_pathq_create": (C.c_int, [_P, C.c_int, C.c_uint64, C.POINTER(_P)]),
+    "pt_pathq_run": (C.c_int, [_P, _P, C.c_uint64, _P, _P]),
+    "pt_pathq_stats": (C.c_int, [_P, C.POINTER(Stats)]),
+    "pt_pathq_free": (None, [_P]),
+    "pt_radiance": (C.c_int, [_P, C.c_int, C.c_uint64, _P, _P, C.POINTER(Stats)]),
+    "pt_camera_rays": (C.c_int, [_P, C.c_uint64, _P, _P]),
     "pt_last_error": (C.c_char_p, []),
     "pt_abi_version": (C.c_int, []),
     "pt_selftest_ray_intersection": (C.c_int, [_P, C.c_int32, C.c_uint32, _P, _P, _P, _P]),
     "pt_selftest_render_host": (C.c_int, [_P, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                           C.c_uint32, _P]),
+    "pt_selftest_paths_host": (C.c_int, [_P, C.c_uint64, _P, _P, _P]),
     "pt_selftest_gamma_table": (C.c_int, [_P, _P]),
     "pt_selftest_wave_plan": (C.c_int, [_P, C.POINTER(SessionOpts), C.c_uint32, C.c_char_p, C.c_size_t]),
     "pt_selftest_math": (C.c_int, [C.c_int, C.c_uint32, C.c_uint64, _P, _P]),
@@ -264,6 +275,25 @@ class Scene:
         _check(_lib.pt_intersect(self._h, device, len(rays), _ptr(rays), _ptr(hits), C.byref(st)))
         return hits, st.as_dict()
 
+    def radiance(self, paths, device=0):
+        """Scene::RayTrace for the caller's rays on the GPU: `paths` is an array of PATH_DTYPE
+        (origin, direction -- used as given --, the seed of the path's fresh random stream,
+        reserved = 0).  Returns (out, stats): out is an array of RADIANCE_DTYPE, rgb = the value
+        RayTrace returns at the scene's RAY_DEPTH, rays = the path's RayIntersection calls."""
+        paths = np.ascontiguousarray(paths, PATH_DTYPE).reshape(-1)
+        out = np.zeros(len(paths), RADIANCE_DTYPE)
+        st = Stats()
+        _check(_lib.pt_radiance(self._h, device, len(paths), _ptr(paths), _ptr(out), C.byref(st)))
+        return out, st.as_dict()
+
+    def camera_rays(self, xy):
+        """Camera::GetToRay for float pixel coordinates: `xy` reshapes to (n, 2) float32; returns
+        (n, 6) float32 rays (origin, direction; the direction is not normalised)."""
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        rays = np.zeros((len(xy), 6), np.float32)
+        _check(_lib.pt_camera_rays(self._h, len(xy), _ptr(xy), _ptr(rays)))
+        return rays
+
     # test hooks (host execution of the device traversal code; not a render path)
     def selftest_ray_intersection(self, rays, traversal=TRAVERSAL_REPLAY, check=True):
         """check=False: a hit-list overflow (the exact DFS's counted condition: the call's error)
@@ -278,6 +308,17 @@ class Scene:
             _check(rc)
         return ids, hits, {"nodes": int(ctr[CTR_NODES]), "prim_tests": int(ctr[CTR_PTESTS]), "aux": int(ctr[CTR_AUX]),
                            "fallbacks": int(ctr[CTR_FALLBACKS]), "errors": int(ctr[CTR_ERRORS])}
+
+    def selftest_paths_host(self, paths):
+        """Scene.radiance's records run on the host (trace_path_with over the query state machine):
+        returns (out, counters), the counters named as pt_stats names them"""
+        paths = np.ascontiguousarray(paths, PATH_DTYPE).reshape(-1)
+        out = np.zeros(len(paths), RADIANCE_DTYPE)
+        ctr = np.zeros(8, np.uint64)
+        _check(_lib.pt_selftest_paths_host(self._h, len(paths), _ptr(paths), _ptr(out), _ptr(ctr)))
+        return out, {"rays": int(ctr[CTR_RAYS]), "node_visits": int(ctr[CTR_NODES]), "prim_tests": int(ctr[CTR_PTESTS]),
+                     "plane_tests": int(ctr[CTR_PLANES]), "errors": int(ctr[CTR_ERRORS]), "aux_visits": int(ctr[CTR_AUX]),
+                     "fallbacks": int(ctr[CTR_FALLBACKS]), "fallbacks_ray": int(ctr[CTR_FALLBACKS_RAY])}
 
     def selftest_render_host(self, x0, y0, w, h, spp=0, traversal=TRAVERSAL_REPLAY):
         rad = np.zeros((h, w, 3), np.float32)
@@ -382,6 +423,45 @@ class RayQuery:
     def close(self):
         if getattr(self, "_h", None) and _lib is not None:
             _lib.pt_rayq_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class PathQuery:
+    """Radiance along paths already on the device (include/pt.h batch radiance): one context per
+    scene and device, for runs of up to max_paths paths."""
+
+    def __init__(self, scene, device=0, max_paths=PATHS_CHUNK):
+        self.scene = scene
+        self.max_paths = max_paths
+        self._h = _P()
+        _check(_lib.pt_pathq_create(scene._h, device, max_paths, C.byref(self._h)))
+
+    def run(self, dev_in, dev_out, n=None, stream=None):
+        """Enqueue n paths on `stream` (a hipStream_t address; None = the null stream).  dev_in /
+        dev_out: 16-byte aligned device addresses, or objects with data_ptr() -- torch tensors of
+        32 bytes per path (PATH_DTYPE) and 16 bytes per result (RADIANCE_DTYPE), used in place; n
+        defaults to the input tensor's size in bytes / 32."""
+        if n is None:
+            n = dev_in.numel() * dev_in.element_size() // 32
+        _check(_lib.pt_pathq_run(self._h, stream, n, _addr(dev_in), _addr(dev_out)))
+
+    def stats(self):
+        """Wait for the last run; the counters and kernel time of the runs since the last call."""
+        st = Stats()
+        _check(_lib.pt_pathq_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.pt_pathq_free(self._h)
             self._h = None
 
     __del__ = close
