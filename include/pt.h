@@ -299,6 +299,66 @@ int pt_radiance(pt_scene* s, int device, uint64_t n, const pt_path_ray* in, pt_p
  * the ray a pixel sample at (x, y) starts with (the direction is not normalised).  Host only. */
 int pt_camera_rays(pt_scene* s, uint64_t n, const float* xy, pt_ray* out);
 
+/* ------------------------------------------------------------ pixel samples
+ * Scene::Sample's loop (src/scene.cpp:189-200) for a list of pixels the caller supplies, bit for
+ * bit (additions to ABI 6: no existing struct or function changed).  No reference counterpart as
+ * an interface: Sample is private to the reference's render, which gives every pixel of the frame
+ * the same SAMPLES.  Here a record is one pixel's state -- its random stream, its f32 sum and its
+ * sample count --, owned by the caller: it may be run for any number of further samples, any
+ * number of times, copied, stored and moved between devices and processes.  Each new sample of a
+ * record is one trip of Sample's loop on the record's ONE stream, as the previous sample left it:
+ *   fx = float(x) + uniform01(rnd);  fy = float(y) + uniform01(rnd);        (scene.cpp:197-198)
+ *   sum = sum + RayTrace(random, cam.GetToRay(fx, fy), RAY_DEPTH);  samples++   (scene.cpp:199)
+ * the sum added component by component in f32, the normal_distribution's saved value carried in
+ * the record.  (At RAY_DEPTH 0 the two jitter draws still happen and the sum gets + 0.)  So a state
+ * run for a and then for b samples equals, bit for bit, one run of a + b; and a fresh default-seed
+ * state taken to S samples resolves to the radiance pt_render and the reference give that pixel at
+ * SAMPLES = S.  A record's samples are serial, as a pixel's are in the reference: a run takes at
+ * least as long as its longest record. */
+typedef struct pt_pixq pt_pixq;
+typedef struct pt_pixel_state {     /* 32 B; arrays 16-byte aligned */
+    uint32_t rng;      /* minstd_rand state, 1 .. 2^31-2; bit 31 set = the pixel's
+                          normal_distribution holds a saved value */
+    float    saved;    /* that value (0 when none) */
+    uint32_t x, y;     /* the pixel: sample k's ray is GetToRay(float(x)+u1, float(y)+u2) */
+    float    sum[3];   /* Sample's `summary`, f32, added in the reference's order */
+    uint32_t samples;  /* samples in sum */
+} pt_pixel_state;
+
+/* Host only.  n fresh states for the pixels xy[2i], xy[2i + 1]: std::minstd_rand rnd(seed) with
+ * fresh distributions (no saved value), sum = 0, samples = 0.  seeds == NULL: the reference's seed
+ * y * W + x (src/scene.cpp:216); else seeds[i], reduced as minstd_rand's constructor reduces it.
+ * x >= W or y >= H: PT_E_INVALID. */
+int pt_pixel_init(pt_scene* s, uint64_t n, const uint32_t* xy, const uint32_t* seeds, pt_pixel_state* out);
+/* a pixel-sample context on `device` for runs of up to max_pixels (1 .. 2^32 - 1) records; prepares
+ * the scene if needed; the scene must outlive the context.  RAY_DEPTH (pt_scene_override applies)
+ * and the camera are read here.  The context holds RAY_DEPTH x 16 B of device memory per resident
+ * lane (PT_E_OOM if one wave per compute unit would pass 1 GiB). */
+int pt_pixq_create(pt_scene* s, int device, uint64_t max_pixels, pt_pixq** out);
+/* asynchronous on `stream` (a hipStream_t; NULL = the null stream).  Record i takes dev_counts[i]
+ * more samples (dev_counts == NULL: spp), and dev_state[i] is updated in place to the state after
+ * them; a count of 0 leaves the record's 32 bytes untouched.  Two records that name the same pixel
+ * are independent.  dev_state is a 16-byte aligned device pointer on the context's device,
+ * dev_counts a device pointer to n u32; n <= max_pixels; n = 0 enqueues nothing.  One run at a
+ * time per context: a run first waits (on the host) for the context's previous run. */
+int pt_pixq_run(pt_pixq* q, void* stream, uint64_t n, pt_pixel_state* dev_state, const uint32_t* dev_counts,
+                uint32_t spp);
+/* waits for the last run; fills samples (those the runs added), rays, node_visits, prim_tests,
+ * plane_tests, aux_visits, fallbacks, fallbacks_ray (over every vertex of every sample), errors
+ * (must be 0), kernel_ms and the *_bytes record sizes for the runs since the last call */
+int pt_pixq_stats(pt_pixq* q, pt_stats* st);
+void pt_pixq_free(pt_pixq* q);
+/* convenience, host pointers, `state` updated in place: uploads, runs, downloads, in chunks of at
+ * most 2^22 records so that device memory stays bounded; synchronous; counts (n u32) may be NULL:
+ * spp for every record; stats may be NULL */
+int pt_sample_pixels(pt_scene* s, int device, uint64_t n, pt_pixel_state* state, const uint32_t* counts,
+                     uint32_t spp, pt_stats* stats);
+/* Host only.  Sample's return value and Render's 8-bit step for n states: mean[3i ..] =
+ * 1.f / samples * sum (src/scene.cpp:201: a product with the rounded reciprocal), rgb[3i ..] = the
+ * tonemap, gamma and rounding of scene.cpp:227-233, computed by the function the device resolve
+ * uses.  Either output may be NULL.  A state with samples == 0: PT_E_INVALID. */
+int pt_pixel_resolve(pt_scene* s, uint64_t n, const pt_pixel_state* state, float* mean, uint8_t* rgb);
+
 const char* pt_last_error(void);
 int pt_abi_version(void);
 
@@ -315,6 +375,12 @@ int pt_selftest_render_host(pt_scene* s, int32_t traversal, uint32_t x0, uint32_
  * rays) and counters8: the totals of rays, nodes, primitive tests, plane tests, errors, aux
  * visits, fallbacks and non-finite-ray fallbacks (the CTR_* slots).  counters8 may be NULL. */
 int pt_selftest_paths_host(pt_scene* s, uint64_t n, const pt_path_ray* in, pt_path_out* out, uint64_t* counters8);
+/* n pixel-sample records on the host, updated in place as pt_pixq_run updates them: camera_ray and
+ * trace_path_with over the query state machine run to completion, on each record's stream.  counts
+ * may be NULL (spp for every record).  counters8 as pt_selftest_paths_host fills it; the samples
+ * added are the counts' sum.  Needs no GPU. */
+int pt_selftest_pixels_host(pt_scene* s, uint64_t n, pt_pixel_state* state, const uint32_t* counts, uint32_t spp,
+                            uint64_t* counters8);
 /* the 256-entry gamma threshold table used by the device tonemap */
 int pt_selftest_gamma_table(const pt_scene* s, float* thr256);
 /* session set-up without a device: the geometry (o's rank, world, window, traversal; o->device is

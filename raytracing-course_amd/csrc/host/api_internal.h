@@ -12,6 +12,8 @@
 //   rayq.cpp      the ray-query engine: closest-hit queries for the caller's rays (pt_rayq_*, pt_intersect)
 //   pathq.cpp     the batch radiance engine: RayTrace for the caller's rays (pt_pathq_*, pt_radiance,
 //                 pt_camera_rays)
+//   pixq.cpp      the pixel-sample engine: Sample's loop for the caller's pixel states (pt_pixq_*,
+//                 pt_sample_pixels, pt_pixel_init, pt_pixel_resolve)
 //   selftest.cpp  host execution of the device query / integrator code, and pt_selftest_math (the
 //                 device code's scalar functions on the host or in k_selftest_math) (tests only; one
 //                 hook, pt_selftest_wave_plan, is in session.cpp beside the set-up it reports)
@@ -37,6 +39,7 @@
 #include "../device/pt_coop.h"
 #include "../device/pt_kernels.h"
 #include "../device/pt_paths.h"
+#include "../device/pt_pixels.h"
 #include "../device/pt_rays.h"
 #include "pt_scene.h"
 
@@ -340,6 +343,23 @@ struct pt_pathq {
     bool pending = false;           // ... whose time has not been added to kernel_ms yet
     double kernel_ms = 0.0;         // since the last pt_pathq_stats
     unsigned long long seen[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the counters at the last pt_pathq_stats
+};
+
+// A pixel-sample context (pixq.cpp): the scene's copy on one device and the run state of k_pixels.
+struct pt_pixq {
+    pt_scene* sc = nullptr;
+    int dev = 0;
+    uint64_t max_pixels = 0;
+    pt::PixelsParams p{};           // the view of the device copy, the camera and the arena's pieces (state, counts,
+                                    // spp, n, batch: per run)
+    // one allocation: the control block | the statistics counters | the resident lanes' fold records
+    unsigned char* arena = nullptr;
+    uint32_t block = 256, max_grid = 1;   // k_pixels' workgroup (its lanes' stacks fit the LDS) and the resident
+                                          // grid, which the fold area is sized for
+    hipEvent_t e0 = nullptr, e1 = nullptr;   // around the last run's kernel
+    bool pending = false;           // ... whose time has not been added to kernel_ms yet
+    double kernel_ms = 0.0;         // since the last pt_pixq_stats
+    unsigned long long seen[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // the counters at the last pt_pixq_stats
 };
 
 #pragma GCC visibility pop

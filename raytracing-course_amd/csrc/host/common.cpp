@@ -114,6 +114,8 @@ const Rccl& rccl() {
 //                     lanes wait (1..64; 1 = on every trip; default PT_RAYS_SERVICE)
 //   paths_service=N   batch radiance (pt_pathq_create): a wave runs its service step (vertices, folds,
 //                     new paths) once N lanes wait (1..64; 1 = on every trip; default PT_PATHS_SERVICE)
+//   pixels_service=N  pixel samples (pt_pixq_create): the same threshold for k_pixels' service step (vertices,
+//                     folds, next samples, new records; 1..64; default PT_PIXELS_SERVICE)
 //   roundlog=1|2|3    per-round kernel times / each round's chains, wall time and rays / and the
 //                     pixels' remaining samples, on stderr
 //   wgprof=FILE       per-workgroup timelines (-DPT_WPROF builds)

@@ -191,6 +191,58 @@ int pt_selftest_paths_host(pt_scene* s, uint64_t n, const pt_path_ray* in, pt_pa
     return C.errs ? fail(PT_E_INVALID, "recomputed closest hit differs from the query's") : PT_OK;
 }
 
+int pt_selftest_pixels_host(pt_scene* s, uint64_t n, pt_pixel_state* state, const uint32_t* counts, uint32_t spp,
+                            uint64_t* counters8) {
+    if (!s) return fail(PT_E_INVALID, "null scene");
+    if (n > 0 && !state) return fail(PT_E_INVALID, "null state buffer");
+    int rc = pt_scene_prepare(s);
+    if (rc) return rc;
+    const pt::SceneView V = host_view(s, PT_TRAVERSAL_REPLAY);
+    const pt::CamView cam = make_cam(s);
+    HostStack stk;
+    HostVStore vs;
+    pt::Counts C{};
+    uint64_t exact_ray = 0;
+    // the pixel-sample engine's query (pt_query.h state machine), run to completion
+    auto q = [&](const pt::Ray& rr, pt::Hit& hh, pt::Counts& cc) {
+        pt::QCounts Q{};
+        uint32_t ex = 0;
+        const int id = pt::q_run(V, rr, stk, hh, Q, ex);
+        cc.fallbacks += ex;
+        const float w = pt::q_prep(V, rr).w;
+        if (w != w) exact_ray++;   // a non-finite ray (q_init_pre: Q_EXACT from the start)
+        if (Q.planes & 0x80000000u) cc.errs |= 4u;   // recomputed hit differs
+        cc.nodes += Q.nodes; cc.ptests += Q.ptests; cc.planes += Q.planes & 0x7fffffffu; cc.aux += Q.aux;
+        return id;
+    };
+    for (uint64_t i = 0; i < n; ++i) {
+        pt_pixel_state& P = state[i];
+        const uint32_t count = counts ? counts[i] : spp;
+        if (count == 0u) continue;   // (not a byte of the record changes)
+        pt::Rng R = pt::pixel_rng(P.rng, P.saved);
+        pt::f3 sum = pt::mk3(P.sum[0], P.sum[1], P.sum[2]);
+        // Sample's loop body (src/scene.cpp:197-199) on the record's stream
+        for (uint32_t k = 0; k < count; ++k) {
+            const float fx = (float)P.x + pt::rng_uniform(R);
+            const float fy = (float)P.y + pt::rng_uniform(R);
+            const pt::Ray ray = pt::camera_ray(cam, fx, fy);
+            sum = sum + pt::trace_path_with(V, q, ray, s->hs.depth, R, vs, C);
+        }
+        P.rng = pt::pixel_rng_word(R);
+        P.saved = pt::pixel_rng_saved(R);
+        P.sum[0] = sum.x; P.sum[1] = sum.y; P.sum[2] = sum.z;
+        P.samples += count;
+    }
+    if (counters8) {
+        uint64_t c[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // (slots CTR_RAYS .. CTR_FALLBACKS_RAY)
+        c[pt::CTR_RAYS] = C.rays; c[pt::CTR_NODES] = C.nodes; c[pt::CTR_PTESTS] = C.ptests; c[pt::CTR_PLANES] = C.planes;
+        c[pt::CTR_ERRORS] = C.errs; c[pt::CTR_AUX] = C.aux; c[pt::CTR_FALLBACKS] = C.fallbacks;
+        c[pt::CTR_FALLBACKS_RAY] = exact_ray;
+        memcpy(counters8, c, sizeof(c));
+    }
+    return C.errs ? fail(PT_E_INVALID, "recomputed closest hit differs from the query's") : PT_OK;
+}
+
 int pt_selftest_gamma_table(const pt_scene* s, float* thr256) {
     if (!s || !s->prepared || !thr256) return fail(PT_E_INVALID, "scene not prepared");
     memcpy(thr256, s->thr, sizeof(s->thr));

@@ -39,6 +39,11 @@ RAYS_CHUNK = 1 << 22   # pt_intersect moves the rays in chunks of at most this m
 PATH_DTYPE = np.dtype([("o", np.float32, (3,)), ("d", np.float32, (3,)), ("seed", np.uint32), ("reserved", np.uint32)])
 RADIANCE_DTYPE = np.dtype([("rgb", np.float32, (3,)), ("rays", np.uint32)])
 PATHS_CHUNK = 1 << 22   # pt_radiance moves the paths in chunks of at most this many
+# a pixel's sampling state (pt_pixel_state, 32 B): rng = the minstd_rand state, bit 31 set = `saved` is the
+# normal_distribution's saved value; sum / samples = Scene::Sample's summary and its loop counter
+PIXEL_DTYPE = np.dtype([("rng", np.uint32), ("saved", np.float32), ("x", np.uint32), ("y", np.uint32),
+                        ("sum", np.float32, (3,)), ("samples", np.uint32)])
+PIXELS_CHUNK = 1 << 22   # pt_sample_pixels moves the records in chunks of at most this many
 # pt_selftest_math's ops (include/pt.h PT_MATH_*): name -> (op, record in, record out; None = 3n f32)
 _VECS = np.dtype([("v", np.float32, (8, 3))])
 MATH_OPS = {
@@ -144,12 +149,20 @@ _sig = {
     "pt_pathq_free": (None, [_P]),
     "pt_radiance": (C.c_int, [_P, C.c_int, C.c_uint64, _P, _P, C.POINTER(Stats)]),
     "pt_camera_rays": (C.c_int, [_P, C.c_uint64, _P, _P]),
+    "pt_pixel_init": (C.c_int, [_P, C.c_uint64, _P, _P, _P]),
+    "pt_pixq_create": (C.c_int, [_P, C.c_int, C.c_uint64, C.POINTER(_P)]),
+    "pt_pixq_run": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint32]),
+    "pt_pixq_stats": (C.c_int, [_P, C.POINTER(Stats)]),
+    "pt_pixq_free": (None, [_P]),
+    "pt_sample_pixels": (C.c_int, [_P, C.c_int, C.c_uint64, _P, _P, C.c_uint32, C.POINTER(Stats)]),
+    "pt_pixel_resolve": (C.c_int, [_P, C.c_uint64, _P, _P, _P]),
     "pt_last_error": (C.c_char_p, []),
     "pt_abi_version": (C.c_int, []),
     "pt_selftest_ray_intersection": (C.c_int, [_P, C.c_int32, C.c_uint32, _P, _P, _P, _P]),
     "pt_selftest_render_host": (C.c_int, [_P, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                           C.c_uint32, _P]),
     "pt_selftest_paths_host": (C.c_int, [_P, C.c_uint64, _P, _P, _P]),
+    "pt_selftest_pixels_host": (C.c_int, [_P, C.c_uint64, _P, _P, C.c_uint32, _P]),
     "pt_selftest_gamma_table": (C.c_int, [_P, _P]),
     "pt_selftest_wave_plan": (C.c_int, [_P, C.POINTER(SessionOpts), C.c_uint32, C.c_char_p, C.c_size_t]),
     "pt_selftest_math": (C.c_int, [C.c_int, C.c_uint32, C.c_uint64, _P, _P]),
@@ -294,6 +307,46 @@ class Scene:
         _check(_lib.pt_camera_rays(self._h, len(xy), _ptr(xy), _ptr(rays)))
         return rays
 
+    def pixel_init(self, xy, seeds=None):
+        """Fresh sampling states (an array of PIXEL_DTYPE) for the pixels `xy` (reshapes to (n, 2)
+        uint32: x, y): the stream std::minstd_rand(seed), sum and samples 0.  seeds=None: the
+        reference's seed y * W + x."""
+        xy = np.ascontiguousarray(xy, np.uint32).reshape(-1, 2)
+        if seeds is not None:
+            seeds = np.ascontiguousarray(seeds, np.uint32).reshape(-1)
+            if len(seeds) != len(xy):
+                raise ValueError("one seed per pixel")
+        state = np.zeros(len(xy), PIXEL_DTYPE)
+        _check(_lib.pt_pixel_init(self._h, len(xy), _ptr(xy), _ptr(seeds), _ptr(state)))
+        return state
+
+    @staticmethod
+    def _pixel_args(state, counts):
+        state = np.ascontiguousarray(state, PIXEL_DTYPE).reshape(-1).copy()
+        if counts is not None:
+            counts = np.ascontiguousarray(counts, np.uint32).reshape(-1)
+            if len(counts) != len(state):
+                raise ValueError("one count per state")
+        return state, counts
+
+    def sample_pixels(self, state, counts=None, spp=0, device=0):
+        """Scene::Sample's loop on the GPU for the caller's pixel states: record i takes counts[i]
+        more samples (counts=None: spp) on its own stream.  Returns (the states after them -- the
+        argument is not changed --, stats)."""
+        state, counts = self._pixel_args(state, counts)
+        st = Stats()
+        _check(_lib.pt_sample_pixels(self._h, device, len(state), _ptr(state), _ptr(counts), spp, C.byref(st)))
+        return state, st.as_dict()
+
+    def pixel_resolve(self, state):
+        """(mean f32 (n, 3), rgb u8 (n, 3)) of the states: Sample's 1.f / samples * sum, and the
+        tonemap, gamma and 8-bit step of the render's resolve."""
+        state = np.ascontiguousarray(state, PIXEL_DTYPE).reshape(-1)
+        mean = np.zeros((len(state), 3), np.float32)
+        rgb = np.zeros((len(state), 3), np.uint8)
+        _check(_lib.pt_pixel_resolve(self._h, len(state), _ptr(state), _ptr(mean), _ptr(rgb)))
+        return mean, rgb
+
     # test hooks (host execution of the device traversal code; not a render path)
     def selftest_ray_intersection(self, rays, traversal=TRAVERSAL_REPLAY, check=True):
         """check=False: a hit-list overflow (the exact DFS's counted condition: the call's error)
@@ -319,6 +372,18 @@ class Scene:
         return out, {"rays": int(ctr[CTR_RAYS]), "node_visits": int(ctr[CTR_NODES]), "prim_tests": int(ctr[CTR_PTESTS]),
                      "plane_tests": int(ctr[CTR_PLANES]), "errors": int(ctr[CTR_ERRORS]), "aux_visits": int(ctr[CTR_AUX]),
                      "fallbacks": int(ctr[CTR_FALLBACKS]), "fallbacks_ray": int(ctr[CTR_FALLBACKS_RAY])}
+
+    def selftest_pixels_host(self, state, counts=None, spp=0):
+        """Scene.sample_pixels' records run on the host (camera_ray and trace_path_with over the query
+        state machine): returns (states, counters), the counters named as pt_stats names them"""
+        state, counts = self._pixel_args(state, counts)
+        ctr = np.zeros(8, np.uint64)
+        _check(_lib.pt_selftest_pixels_host(self._h, len(state), _ptr(state), _ptr(counts), spp, _ptr(ctr)))
+        added = int(counts.sum(dtype=np.uint64)) if counts is not None else spp * len(state)
+        return state, {"rays": int(ctr[CTR_RAYS]), "node_visits": int(ctr[CTR_NODES]), "prim_tests": int(ctr[CTR_PTESTS]),
+                       "plane_tests": int(ctr[CTR_PLANES]), "errors": int(ctr[CTR_ERRORS]), "aux_visits": int(ctr[CTR_AUX]),
+                       "fallbacks": int(ctr[CTR_FALLBACKS]), "fallbacks_ray": int(ctr[CTR_FALLBACKS_RAY]),
+                       "samples": added}
 
     def selftest_render_host(self, x0, y0, w, h, spp=0, traversal=TRAVERSAL_REPLAY):
         rad = np.zeros((h, w, 3), np.float32)
@@ -462,6 +527,46 @@ class PathQuery:
     def close(self):
         if getattr(self, "_h", None) and _lib is not None:
             _lib.pt_pathq_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class PixelQuery:
+    """Further samples for pixel states already on the device (include/pt.h pixel samples): one
+    context per scene and device, for runs of up to max_pixels records."""
+
+    def __init__(self, scene, device=0, max_pixels=PIXELS_CHUNK):
+        self.scene = scene
+        self.max_pixels = max_pixels
+        self._h = _P()
+        _check(_lib.pt_pixq_create(scene._h, device, max_pixels, C.byref(self._h)))
+
+    def run(self, dev_state, counts=None, spp=0, n=None, stream=None):
+        """Enqueue n records on `stream` (a hipStream_t address; None = the null stream).  dev_state:
+        a 16-byte aligned device address, or an object with data_ptr() -- a torch tensor of 32
+        bytes per record (PIXEL_DTYPE), updated in place; counts: the same for n uint32 (int32
+        tensors of non-negative values serve), or None: spp for every record; n defaults to the
+        state tensor's size in bytes / 32."""
+        if n is None:
+            n = dev_state.numel() * dev_state.element_size() // 32
+        _check(_lib.pt_pixq_run(self._h, stream, n, _addr(dev_state), None if counts is None else _addr(counts), spp))
+
+    def stats(self):
+        """Wait for the last run; the counters and kernel time of the runs since the last call."""
+        st = Stats()
+        _check(_lib.pt_pixq_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.pt_pixq_free(self._h)
             self._h = None
 
     __del__ = close
