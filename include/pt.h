@@ -237,6 +237,42 @@ int pt_session_stats(pt_session* ss, pt_stats* st);
 void* pt_session_stream(pt_session* ss);
 void pt_session_free(pt_session* ss);
 
+/* ------------------------------------------------------- session states
+ * A session's pixels as pt_pixel_state records (below, "pixel samples") and back: the hand-over
+ * between the two owners of a pixel's state (additions to ABI 6: no existing struct or function
+ * changed).  No reference counterpart: the reference's render cannot be interrupted.  A record a
+ * session exports is byte for byte the record pt_pixq_run leaves for that pixel after the same
+ * samples -- the saved-value flag in bit 31 of rng, saved = +0 when nothing is saved, samples = the
+ * session's count --, so a frame may be checkpointed and resumed, moved to another number of ranks,
+ * started from the caller's seeds, or traced in bulk here and refined with pt_pixq_run.
+ * pt_session_stats().samples stays owned pixels x samples so far, imported samples included; the
+ * work counters (rays, node_visits, ...) count this session's own tracing only. */
+typedef struct pt_pixel_state pt_pixel_state;
+/* pixels this session owns (inside its window) */
+int pt_session_pixels(const pt_session* ss, uint64_t* n);
+/* Every owned pixel as a pt_pixel_state, in slot order: the session's tiles in ascending tile
+ * order, a tile's pixels row-major, pixels outside the window left out -- exactly
+ * pt_session_pixels records, each with the image's global x, y.  Runs any trace() not yet run
+ * first.  dev_state: 16-byte aligned device pointer on the session's device, room for cap
+ * records; cap < the count: PT_E_INVALID, nothing written.  Complete on return. */
+int pt_session_export(pt_session* ss, pt_pixel_state* dev_state, uint64_t cap);
+/* Replace the session's pixels by the caller's states.  Records may come in any order.  A
+ * record whose pixel lies in the image but is not this session's (another rank's tile, outside
+ * the window) is skipped; *taken (may be NULL; written on success only) = records taken.
+ * Refused with PT_E_INVALID, the session left exactly as it was, when: a record has x >= W or
+ * y >= H; a taken record's rng has low 31 bits outside 1 .. 2^31-2; an owned pixel is named by no
+ * record or by more than one; the taken records' `samples` are not all equal.  On success the
+ * session stands at that common sample count S: the next trace(k) takes every pixel from S to
+ * S + k on the imported streams, and resolve divides by S + k.  S = 0 is allowed (fresh states
+ * with the caller's seeds).  A taken record's `saved` is read only when its flag is set; its sum is
+ * taken as given (non-finite values too).  A session that owns no pixel takes none of any list.
+ * Runs any trace() not yet run first.  Every record is checked before the first is written: the
+ * records must not change during the call.  Complete on return. */
+int pt_session_import(pt_session* ss, uint64_t n, const pt_pixel_state* dev_state, uint64_t* taken);
+/* the same with host pointers (upload / download inside; no alignment asked) */
+int pt_session_export_host(pt_session* ss, pt_pixel_state* state, uint64_t cap);
+int pt_session_import_host(pt_session* ss, uint64_t n, const pt_pixel_state* state, uint64_t* taken);
+
 /* ------------------------------------------------------------ ray queries
  * Scene::RayIntersection (src/scene.cpp:46-77) for the caller's own rays, bit for bit: the
  * planes, then the reference BVH with its pruning semantics (first-hit buffers, picking,
@@ -390,6 +426,12 @@ int pt_selftest_gamma_table(const pt_scene* s, float* thr256);
  * aux_stack_words (the scene's wide aux traversal stack, which a carry record holds).
  * Prepares the scene if needed. */
 int pt_selftest_wave_plan(pt_scene* s, const pt_session_opts* o, uint32_t cus, char* buf, size_t cap);
+/* per record the session slot it would land in, by the functions k_states_mark uses compiled
+ * for the host: >= 0 slot, -1 in the image but not this session's, -2 outside the image or a
+ * bad rng word (of a pixel that is this session's: another's record is -1 whatever it holds).
+ * o as pt_selftest_wave_plan takes it.  Needs no GPU. */
+int pt_selftest_state_slots(pt_scene* s, const pt_session_opts* o, uint64_t n, const pt_pixel_state* state,
+                            int64_t* slot_out);
 /* The scalar building blocks of the device code (logf, the RNG streams, the normal and cosine
  * samplers, the Schlick term, the resolve's mean + tonemap + 8-bit step, IEEE divide / sqrt /
  * conversions), element by element: n records in, n records out (little-endian, packed).

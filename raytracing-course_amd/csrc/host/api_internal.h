@@ -14,6 +14,8 @@
 //                 pt_camera_rays)
 //   pixq.cpp      the pixel-sample engine: Sample's loop for the caller's pixel states (pt_pixq_*,
 //                 pt_sample_pixels, pt_pixel_init, pt_pixel_resolve)
+//   states.cpp    a session's pixels out as pixel states and in again (pt_session_pixels / export / import),
+//                 and the import's classification on the host (pt_selftest_state_slots)
 //   selftest.cpp  host execution of the device query / integrator code, and pt_selftest_math (the
 //                 device code's scalar functions on the host or in k_selftest_math) (tests only; one
 //                 hook, pt_selftest_wave_plan, is in session.cpp beside the set-up it reports)
@@ -144,6 +146,8 @@ double wall_ms();
 int finish_pending(pt_session* ss);
 std::vector<uint32_t> rank_tiles(uint32_t n_tiles, uint32_t tiles_x, uint32_t rank, uint32_t world);
 uint64_t owned_pixels(const pt_session* ss);
+// a session's geometry without a device (tm -- its gtile left null --, gtiles, n_tiles_local, n_slots)
+int session_geometry_only(pt_scene* s, const pt_session_opts* o, pt_session* ss);
 hipError_t read_counters(pt_session* ss, unsigned long long c[PT_CTR_STRIDE]);
 int flush_trace(pt_session* ss);
 int trace_wave(pt_session* ss, uint32_t spp);
@@ -312,6 +316,10 @@ struct pt_session {
     unsigned long long* prog_dev = nullptr;
     pt::CamView cam{};
     int traversal = PT_TRAVERSAL_REPLAY;
+    // state exchange (states.cpp), allocations of their own made at the first export / import:
+    // the export's first record per local tile; the import's result block and per-slot marks
+    uint32_t* state_tile_rec = nullptr;
+    unsigned char* state_marks = nullptr;
 };
 
 // A ray-query context (rayq.cpp): the scene's copy on one device and the run state of k_rays.

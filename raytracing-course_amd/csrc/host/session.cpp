@@ -291,6 +291,11 @@ int unpack_tiles(uint32_t W, uint32_t H, uint32_t rank, uint32_t world, const T*
 }
 
 }  // namespace
+
+int session_geometry_only(pt_scene* s, const pt_session_opts* o, pt_session* ss) {
+    std::vector<uint32_t> ord;
+    return session_geometry(s, o, ss, &ord);
+}
 }  // namespace pti
 
 using namespace pti;
@@ -579,6 +584,7 @@ void pt_session_free(pt_session* ss) {
     finish_pending(ss);
     (void)hipFree(ss->arena);
     (void)hipFree(ss->rad); (void)hipFree(ss->wg_prof);
+    (void)hipFree(ss->state_tile_rec); (void)hipFree(ss->state_marks);
     if (ss->ctl_host) (void)hipHostFree(ss->ctl_host);
     if (ss->prog_host) (void)hipHostFree(ss->prog_host);
     if (ss->side_taken) (void)hipEventDestroy(ss->side_taken);

@@ -138,6 +138,11 @@ _sig = {
     "pt_session_stats": (C.c_int, [_P, C.POINTER(Stats)]),
     "pt_session_stream": (_P, [_P]),
     "pt_session_free": (None, [_P]),
+    "pt_session_pixels": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "pt_session_export": (C.c_int, [_P, _P, C.c_uint64]),
+    "pt_session_import": (C.c_int, [_P, C.c_uint64, _P, C.POINTER(C.c_uint64)]),
+    "pt_session_export_host": (C.c_int, [_P, _P, C.c_uint64]),
+    "pt_session_import_host": (C.c_int, [_P, C.c_uint64, _P, C.POINTER(C.c_uint64)]),
     "pt_rayq_create": (C.c_int, [_P, C.c_int, C.c_uint64, C.POINTER(_P)]),
     "pt_rayq_run": (C.c_int, [_P, _P, C.c_uint64, _P, _P]),
     "pt_rayq_stats": (C.c_int, [_P, C.POINTER(Stats)]),
@@ -165,6 +170,7 @@ _sig = {
     "pt_selftest_pixels_host": (C.c_int, [_P, C.c_uint64, _P, _P, C.c_uint32, _P]),
     "pt_selftest_gamma_table": (C.c_int, [_P, _P]),
     "pt_selftest_wave_plan": (C.c_int, [_P, C.POINTER(SessionOpts), C.c_uint32, C.c_char_p, C.c_size_t]),
+    "pt_selftest_state_slots": (C.c_int, [_P, C.POINTER(SessionOpts), C.c_uint64, _P, _P]),
     "pt_selftest_math": (C.c_int, [C.c_int, C.c_uint32, C.c_uint64, _P, _P]),
 }
 for _name, (_res, _args) in _sig.items():
@@ -400,6 +406,16 @@ class Scene:
         kv = (line.split("=") for line in buf.value.decode().splitlines())
         return {k: tuple(int(x) for x in v.split(",")) if "," in v else int(v) for k, v in kv}
 
+    def selftest_state_slots(self, state, rank=0, world=1, traversal=TRAVERSAL_REPLAY, window=None):
+        """Per record of `state` the slot of a (rank, world, window) session that Session.import_states
+        would write it to, by the import kernels' own functions run on the host: >= 0 a slot, -1 a
+        pixel of the image that is not that session's, -2 outside the image or a bad rng word."""
+        state = np.ascontiguousarray(state, PIXEL_DTYPE).reshape(-1)
+        o = SessionOpts(0, rank, world, traversal, *(window or (0, 0, 0, 0)))
+        slots = np.zeros(len(state), np.int64)
+        _check(_lib.pt_selftest_state_slots(self._h, C.byref(o), len(state), _ptr(state), _ptr(slots)))
+        return slots
+
     def gamma_table(self):
         t = np.zeros(256, np.float32)
         _check(_lib.pt_selftest_gamma_table(self._h, _ptr(t)))
@@ -446,6 +462,40 @@ class Session:
     @property
     def stream(self):
         return _lib.pt_session_stream(self._h)
+
+    @property
+    def n_pixels(self):
+        """the pixels this session owns: the records of an export"""
+        n = C.c_uint64()
+        _check(_lib.pt_session_pixels(self._h, C.byref(n)))
+        return n.value
+
+    def export_states(self, dev=None):
+        """Every owned pixel's sampling state, in slot order (rank_pixels' order): an array of
+        PIXEL_DTYPE, or with `dev` -- a 16-byte aligned device address or an object with data_ptr(),
+        room for n_pixels records of 32 bytes -- a fill of it (returns dev)."""
+        n = self.n_pixels
+        if dev is not None:
+            _check(_lib.pt_session_export(self._h, _addr(dev), n))
+            return dev
+        state = np.zeros(n, PIXEL_DTYPE)
+        _check(_lib.pt_session_export_host(self._h, _ptr(state), n))
+        return state
+
+    def import_states(self, state, n=None):
+        """Replace the owned pixels by the caller's states: a numpy array of PIXEL_DTYPE, or a device
+        address / an object with data_ptr() holding n records (n defaults to the object's size in
+        bytes / 32).  Records of pixels that are not this session's are skipped; returns the number
+        taken.  Every owned pixel must be named once, all at one sample count (include/pt.h)."""
+        taken = C.c_uint64()
+        if isinstance(state, np.ndarray):
+            state = np.ascontiguousarray(state, PIXEL_DTYPE).reshape(-1)
+            _check(_lib.pt_session_import_host(self._h, len(state) if n is None else n, _ptr(state), C.byref(taken)))
+        else:
+            if n is None:
+                n = state.numel() * state.element_size() // 32
+            _check(_lib.pt_session_import(self._h, n, _addr(state), C.byref(taken)))
+        return taken.value
 
     def close(self):
         if getattr(self, "_h", None) and _lib is not None:
@@ -587,6 +637,19 @@ def rank_tiles(width, height, rank, world):
     """the window tiles of `rank`, in its local (ascending) order"""
     tiles_x, tiles_y = (width + 15) // 16, (height + 15) // 16
     return [t for t in range(tiles_x * tiles_y) if tile_owner(t, tiles_x, world) == rank]
+
+
+def rank_pixels(width, height, rank, world, x0=0, y0=0):
+    """the (n, 2) uint32 global x, y of the pixels a session of `rank` owns in a width x height
+    window at (x0, y0), in the order Session.export_states gives their records: the rank's tiles
+    ascending, a tile's pixels row-major, without the pixels an edge tile lacks"""
+    tiles_x = (width + 15) // 16
+    out = []
+    for t in rank_tiles(width, height, rank, world):
+        tx, ty = 16 * (t % tiles_x), 16 * (t // tiles_x)
+        ys, xs = np.mgrid[ty:min(ty + 16, height), tx:min(tx + 16, width)]
+        out.append(np.stack([x0 + xs.ravel(), y0 + ys.ravel()], axis=1))
+    return np.concatenate(out).astype(np.uint32) if out else np.zeros((0, 2), np.uint32)
 
 
 def unpack_tiles(packed, width, height, rank, world, out=None):
