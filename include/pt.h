@@ -273,6 +273,38 @@ int pt_session_import(pt_session* ss, uint64_t n, const pt_pixel_state* dev_stat
 int pt_session_export_host(pt_session* ss, pt_pixel_state* state, uint64_t cap);
 int pt_session_import_host(pt_session* ss, uint64_t n, const pt_pixel_state* state, uint64_t* taken);
 
+/* Per-pixel sample counts: adaptive passes on the session's own engines (additions to ABI 6).
+ * Pixel i of the session -- in pt_session_export's order -- takes dev_counts[i] more samples
+ * (any u32; 0 leaves the pixel's state untouched, bit for bit).  n must equal pt_session_pixels.
+ * Runs any trace() not yet run first, then one pass of the session's own engines; asynchronous on
+ * the session's stream like a pass; dev_counts must not change before the next sync point
+ * (sync / resolve / stats / export / import).  After it the session is "ragged": pixels hold
+ * different sample counts.
+ *   A ragged session: a pixel that has taken k samples in all holds exactly the state pt_pixq_run
+ * leaves after k samples, and pt_session_export returns it byte for byte, `samples` = the pixel's
+ * own count.  pt_session_trace(spp) adds spp to every pixel (and coalesces as always).
+ * pt_session_resolve divides each pixel's sum by its own count, as pt_pixel_resolve does, and
+ * returns PT_E_INVALID -- nothing written, the session intact -- while an owned pixel has no sample;
+ * its lost-chain check is as strict as ever: every owned pixel must stand exactly at the count the
+ * session expects of it (pt_stats.short_pixels counts the others).  pt_session_stats().samples is
+ * the owned pixels' counts summed, imported samples included; the work counters count this
+ * session's own tracing.  pt_session_reset, and a pt_session_import (which goes on refusing
+ * unequal counts), leave a uniform session.
+ *   Refused with PT_E_INVALID, the session left exactly as it was: n is not the session's pixel
+ * count; dev_counts is NULL with n > 0; a pixel's count would pass 2^32 - 1.  A session that owns
+ * no pixel accepts n = 0.  All-zero counts launch no pass and change nothing.
+ *   Scope: the wavefront engines only.  A megakernel session (traversal EXACT or REPLAY_DIV, or
+ * PT_TUNE engine=mega) returns PT_E_INVALID from these calls: k_trace advances by a uniform spp. */
+int pt_session_trace_counts(pt_session* ss, uint64_t n, const uint32_t* dev_counts);
+int pt_session_trace_counts_host(pt_session* ss, uint64_t n, const uint32_t* counts);
+/* pt_session_import without the equal-`samples` rule: every other rule, and the all-or-nothing
+ * refusal, as pt_session_import has them.  Each pixel goes on from its record's own count. */
+int pt_session_import_ragged(pt_session* ss, uint64_t n, const pt_pixel_state* dev_state, uint64_t* taken);
+int pt_session_import_ragged_host(pt_session* ss, uint64_t n, const pt_pixel_state* state, uint64_t* taken);
+/* the smallest and the largest sample count of the session's pixels, trace() calls not yet run
+ * included (equal: a uniform session).  Host bookkeeping: no device work, no sync point. */
+int pt_session_samples_range(const pt_session* ss, uint32_t* least, uint32_t* most);
+
 /* ------------------------------------------------------------ ray queries
  * Scene::RayIntersection (src/scene.cpp:46-77) for the caller's own rays, bit for bit: the
  * planes, then the reference BVH with its pruning semantics (first-hit buffers, picking,
@@ -432,6 +464,17 @@ int pt_selftest_wave_plan(pt_scene* s, const pt_session_opts* o, uint32_t cus, c
  * o as pt_selftest_wave_plan takes it.  Needs no GPU. */
 int pt_selftest_state_slots(pt_scene* s, const pt_session_opts* o, uint64_t n, const pt_pixel_state* state,
                             int64_t* slot_out);
+/* per slot of the session (o as pt_selftest_wave_plan takes it) the record of its export that holds
+ * the slot's pixel -- pt_session_trace_counts' count for it --, -1 for an edge tile's padding lane,
+ * by the function the count kernels use compiled for the host.  *n_slots = the session's slots;
+ * rec_out has room for cap (fewer than the slots: PT_E_INVALID).  Needs no GPU. */
+int pt_selftest_count_records(pt_scene* s, const pt_session_opts* o, uint64_t cap, int64_t* rec_out, uint64_t* n_slots);
+/* one pt_session_trace_counts call's arithmetic on the host, for n pixels of a session whose
+ * `done` fields stand at S with the pixels' counts lag[i] below it: *S2 = the pass's target (the
+ * largest count after the call; past 2^32 - 1: PT_E_INVALID, nothing written), done[i] = the field
+ * the pass starts pixel i from, lag_after[i] = its distance below S2 afterwards.  Needs no GPU. */
+int pt_selftest_count_step(uint32_t S, uint64_t n, const uint32_t* lag, const uint32_t* counts, uint32_t* done,
+                           uint32_t* lag_after, uint32_t* S2);
 /* The scalar building blocks of the device code (logf, the RNG streams, the normal and cosine
  * samplers, the Schlick term, the resolve's mean + tonemap + 8-bit step, IEEE divide / sqrt /
  * conversions), element by element: n records in, n records out (little-endian, packed).

@@ -69,6 +69,7 @@ enum : uint32_t {
     SR_MAX = 3u,        // the taken records' largest `samples` ...
     SR_NMIN = 4u,       // ... and the complement of their smallest (so that zero is "none yet")
     SR_MISMARKED = 5u,  // owned slots named by no taken record or by more than one
+    SR_LAG_SUM = 6u,    // a ragged import's write (pt_counts.hip): the taken records' distances below SR_MAX, summed
     SR_WORDS = 8u
 };
 
@@ -81,6 +82,7 @@ struct StatesParams {
     unsigned long long n;         // import: records
     uint32_t* mark;               // import: per slot, the taken records that name it
     unsigned long long* res;      // import: SR_* words
+    const uint32_t* lag;          // export: per slot, what its pixel's count lies below `done` (pt_counts.h; null: nothing)
 };
 
 }  // namespace pt

@@ -35,6 +35,7 @@ __global__ void __launch_bounds__(256) k_states_export(StatesParams P) {
     const uint32_t w = state_tile_width(P.tm, P.tm.gtile[tile]);
     uint4 a, b;
     slot_to_state(P.st.rec[2u * slot], P.st.rec[2u * slot + 1u], x, y, a, b);
+    if (P.lag) b.w -= P.lag[slot];   // (a ragged session: `done` is the session's virtual count)
     uint4* out = reinterpret_cast<uint4*>(P.state + ((size_t)P.tile_rec[tile] + (lane >> 4) * w + (lane & 15u)));
     out[0] = a;
     out[1] = b;

@@ -16,6 +16,8 @@
 //                 pt_sample_pixels, pt_pixel_init, pt_pixel_resolve)
 //   states.cpp    a session's pixels out as pixel states and in again (pt_session_pixels / export / import),
 //                 and the import's classification on the host (pt_selftest_state_slots)
+//   counts.cpp    per-pixel sample counts in a session (pt_session_trace_counts / import_ragged /
+//                 samples_range), and the slot -> record map on the host (pt_selftest_count_records)
 //   selftest.cpp  host execution of the device query / integrator code, and pt_selftest_math (the
 //                 device code's scalar functions on the host or in k_selftest_math) (tests only; one
 //                 hook, pt_selftest_wave_plan, is in session.cpp beside the set-up it reports)
@@ -151,6 +153,23 @@ int session_geometry_only(pt_scene* s, const pt_session_opts* o, pt_session* ss)
 hipError_t read_counters(pt_session* ss, unsigned long long c[PT_CTR_STRIDE]);
 int flush_trace(pt_session* ss);
 int trace_wave(pt_session* ss, uint32_t spp);
+// states.cpp: the state-exchange buffers (made at the first use), and an import's validation of the
+// caller's n records -- nothing of the session written; res: the SR_* words of pt_states.h
+std::vector<uint32_t> tile_records(const pt_session* ss);   // the export's first record of every local tile
+int ensure_export(pt_session* ss);
+int validate_import(pt_session* ss, uint64_t n, const pt_pixel_state* dev_state, unsigned long long* res);
+int check_state_pointer(const void* p);
+// a device buffer of n records for the host-pointer forms
+struct DevRecords {
+    void* p = nullptr;
+    ~DevRecords() { (void)hipFree(p); }
+    int alloc(uint64_t n);
+};
+// counts.cpp: a ragged session's lag table (null: none yet), zeroed -- the session is uniform again;
+// the resolve with every pixel's own count (a ragged session's pt_session_resolve launch)
+uint32_t* lag_table(const pt_session* ss);
+hipError_t clear_lag(pt_session* ss);
+hipError_t launch_ragged_resolve(pt_session* ss, uint8_t* out, float* rad);
 pt::SceneView device_view(const pt_session* ss);
 pt::SceneView device_view(const pt_scene* s, const DevScene& ds);   // ... of any device copy (rayq.cpp)
 // the hand-off site named `name` (PT_HO_*: "suspend", "flush", "ringout", "exact", "side_take",
@@ -320,6 +339,15 @@ struct pt_session {
     // the export's first record per local tile; the import's result block and per-slot marks
     uint32_t* state_tile_rec = nullptr;
     unsigned char* state_marks = nullptr;
+    // per-pixel sample counts (counts.cpp), allocations of their own made at the first
+    // ragged call: the result block with the per-slot lag table behind it -- every owned pixel's
+    // `done` stands at samples_done, its own count is samples_done - lag[slot] --, and the host
+    // form's copy of the caller's counts.  lag_sum / lag_max: the owned slots' lags, summed and
+    // their largest (0: every pixel stands at samples_done, the session is uniform)
+    unsigned char* counts_block = nullptr;
+    uint32_t* counts_host_copy = nullptr;
+    uint64_t lag_sum = 0;
+    uint32_t lag_max = 0;
 };
 
 // A ray-query context (rayq.cpp): the scene's copy on one device and the run state of k_rays.

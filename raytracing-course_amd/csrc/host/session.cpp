@@ -454,6 +454,10 @@ int pt_session_resolve(pt_session* ss, uint8_t* dev_out, float* dev_radiance) {
     if (!ss) return fail(PT_E_INVALID, "null session");
     if (ss->n_tiles_local == 0) return PT_OK;
     if (const int rc = flush_trace(ss)) return rc;
+    // a ragged session (counts.cpp) divides each pixel's sum by its own count: none may be 0
+    const bool ragged = ss->lag_max != 0;
+    if (ragged && ss->lag_max == ss->samples_done)
+        return fail(PT_E_INVALID, "an owned pixel has no sample yet: its mean is undefined (as pt_pixel_resolve refuses it)");
     HIP_TRY(hipSetDevice(ss->dev));
     pt::ResolveParams rp;
     rp.st = ss->st;
@@ -467,7 +471,8 @@ int pt_session_resolve(pt_session* ss, uint8_t* dev_out, float* dev_radiance) {
     HIP_TRY(hipEventCreate(&e0));
     HIP_TRY(hipEventCreate(&e1));
     HIP_TRY(hipEventRecord(e0, ss->stream));
-    HIP_TRY(pt_launch_resolve(rp, ss->n_tiles_local, ss->stream));
+    if (ragged) HIP_TRY(launch_ragged_resolve(ss, rp.out, rp.rad));
+    else HIP_TRY(pt_launch_resolve(rp, ss->n_tiles_local, ss->stream));
     HIP_TRY(hipEventRecord(e1, ss->stream));
     HIP_TRY(hipStreamSynchronize(ss->stream));
     float ms = 0.f;
@@ -483,7 +488,10 @@ int pt_session_resolve(pt_session* ss, uint8_t* dev_out, float* dev_radiance) {
         if (tune_int("shortlog", 0)) {
             // diagnostics: how far the short pixels are from the target, and where they are
             std::vector<uint4> rec(2ull * ss->n_slots);
-            if (hipMemcpy(rec.data(), ss->st.rec, rec.size() * sizeof(uint4), hipMemcpyDeviceToHost) == hipSuccess) {
+            // (a ragged session: a pixel's own count lies lag[slot] below its `done` field)
+            std::vector<uint32_t> lag(ss->n_slots, 0u);
+            if (hipMemcpy(rec.data(), ss->st.rec, rec.size() * sizeof(uint4), hipMemcpyDeviceToHost) == hipSuccess &&
+                (!ragged || hipMemcpy(lag.data(), lag_table(ss), lag.size() * 4, hipMemcpyDeviceToHost) == hipSuccess)) {
                 std::map<int, uint32_t> hist;
                 uint32_t shown = 0;
                 for (uint32_t i = 0; i < ss->n_slots; ++i) {
@@ -491,12 +499,14 @@ int pt_session_resolve(pt_session* ss, uint8_t* dev_out, float* dev_radiance) {
                     if (done == rp.samples || rec[2 * i + 1].w == 0xFFFFFFFFu) continue;
                     hist[(int)done - (int)rp.samples]++;
                     if (shown++ < 8)
-                        fprintf(stderr, "short: slot %u pixel %u done %u nv %u\n", i, rec[2 * i + 1].w, done, nv);
+                        fprintf(stderr, "short: slot %u pixel %u done %u of %u nv %u\n", i, rec[2 * i + 1].w, done - lag[i],
+                                rp.samples - lag[i], nv);
                 }
                 for (auto& h : hist) fprintf(stderr, "short: done - samples = %d: %u pixels\n", h.first, h.second);
             }
         }
-        return fail(PT_E_HIP, std::to_string(k) + " pixel(s) did not take exactly " + std::to_string(rp.samples) +
+        return fail(PT_E_HIP, std::to_string(k) + " pixel(s) did not take exactly " +
+                                  (ragged ? std::string("their own count of") : std::to_string(rp.samples)) +
                                   " samples (a chain was lost)");
     }
     return PT_OK;
@@ -520,6 +530,7 @@ int pt_session_reset(pt_session* ss) {
         ip.st = ss->st;
         HIP_TRY(pt_launch_init(ip, ss->n_tiles_local, ss->stream));
     }
+    HIP_TRY(clear_lag(ss));   // (a ragged session: uniform again)
     ss->samples_done = 0;
     return PT_OK;
 }
@@ -542,7 +553,7 @@ int pt_session_stats(pt_session* ss, pt_stats* st) {
     HIP_TRY(read_counters(ss, c));
     memset(st, 0, sizeof(*st));
     counter_stats(c, st);
-    st->samples = owned_pixels(ss) * ss->samples_done;
+    st->samples = owned_pixels(ss) * ss->samples_done - ss->lag_sum;   // (lag_sum: a ragged session's, counts.cpp)
     st->kernel_ms = ss->kernel_ms;
     st->resolve_ms = ss->resolve_ms;
     st->node_bytes = sizeof(pt::Node);
@@ -585,6 +596,7 @@ void pt_session_free(pt_session* ss) {
     (void)hipFree(ss->arena);
     (void)hipFree(ss->rad); (void)hipFree(ss->wg_prof);
     (void)hipFree(ss->state_tile_rec); (void)hipFree(ss->state_marks);
+    (void)hipFree(ss->counts_block); (void)hipFree(ss->counts_host_copy);
     if (ss->ctl_host) (void)hipHostFree(ss->ctl_host);
     if (ss->prog_host) (void)hipHostFree(ss->prog_host);
     if (ss->side_taken) (void)hipEventDestroy(ss->side_taken);

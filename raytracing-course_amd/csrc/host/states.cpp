@@ -9,7 +9,6 @@
 #include "../device/pt_states.h"
 
 namespace pti {
-namespace {
 
 // the export's first record of every local tile (edge tiles hold fewer than 256 pixels)
 std::vector<uint32_t> tile_records(const pt_session* ss) {
@@ -37,6 +36,8 @@ int ensure_export(pt_session* ss) {
     ss->state_tile_rec = static_cast<uint32_t*>(p);
     return PT_OK;
 }
+
+namespace {
 constexpr size_t kResBytes = 256;   // the result block (SR_WORDS u64), the mark array behind it
 static_assert(pt::SR_WORDS * 8u <= kResBytes, "the import's result block outgrew its section");
 int ensure_import(pt_session* ss) {
@@ -57,12 +58,15 @@ pt::StatesParams params(const pt_session* ss, pt_pixel_state* state, uint64_t n)
     p.tile_rec = ss->state_tile_rec;
     p.state = reinterpret_cast<pt::PixelRec*>(state);
     p.n = n;
+    p.lag = lag_table(ss);
     if (ss->state_marks) {
         p.res = reinterpret_cast<unsigned long long*>(ss->state_marks);
         p.mark = reinterpret_cast<uint32_t*>(ss->state_marks + kResBytes);
     }
     return p;
 }
+
+}  // namespace
 
 int check_state_pointer(const void* p) {
     if (!p) return fail(PT_E_INVALID, "null state buffer");
@@ -71,18 +75,34 @@ int check_state_pointer(const void* p) {
     return PT_OK;
 }
 
-// a device buffer of n records for the host-pointer forms
-struct DevRecords {
-    void* p = nullptr;
-    ~DevRecords() { (void)hipFree(p); }
-    int alloc(uint64_t n) {
-        if (hipMalloc(&p, std::max<uint64_t>(n, 1) * sizeof(pt_pixel_state)) != hipSuccess)
-            return fail(PT_E_OOM, "device allocation failed (state records)");
-        return PT_OK;
-    }
-};
+int DevRecords::alloc(uint64_t n) {
+    if (hipMalloc(&p, std::max<uint64_t>(n, 1) * sizeof(pt_pixel_state)) != hipSuccess)
+        return fail(PT_E_OOM, "device allocation failed (state records)");
+    return PT_OK;
+}
 
-}  // namespace
+// An import's validation (the session has pixels, n > 0, its device current): every record classified
+// and counted, every owned slot's marks checked, the result on the host.  Nothing of the session has
+// changed when it returns, whatever it returns.
+int validate_import(pt_session* ss, uint64_t n, const pt_pixel_state* dev_state, unsigned long long* res) {
+    if (const int rc = ensure_import(ss)) return rc;
+    const pt::StatesParams p = params(ss, const_cast<pt_pixel_state*>(dev_state), n);
+    HIP_TRY(hipMemsetAsync(ss->state_marks, 0, kResBytes + (size_t)ss->n_slots * 4, ss->stream));
+    HIP_TRY(pt_launch_states_mark(p, ss->stream));
+    HIP_TRY(pt_launch_states_check(p, ss->stream));
+    HIP_TRY(hipMemcpyAsync(res, p.res, pt::SR_WORDS * 8u, hipMemcpyDeviceToHost, ss->stream));
+    HIP_TRY(hipStreamSynchronize(ss->stream));
+    if (res[pt::SR_OUTSIDE])
+        return fail(PT_E_INVALID, std::to_string(res[pt::SR_OUTSIDE]) + " record(s) name a pixel outside the image");
+    if (res[pt::SR_BAD_RNG])
+        return fail(PT_E_INVALID, std::to_string(res[pt::SR_BAD_RNG]) + " record(s) of the session's pixels have an rng " +
+                                      "word outside 1 .. 2^31-2");
+    if (res[pt::SR_MISMARKED])
+        return fail(PT_E_INVALID, std::to_string(res[pt::SR_MISMARKED]) + " of the session's pixels are named by no " +
+                                      "record or by more than one");
+    return PT_OK;
+}
+
 }  // namespace pti
 
 using namespace pti;
@@ -122,29 +142,17 @@ int pt_session_import(pt_session* ss, uint64_t n, const pt_pixel_state* dev_stat
     }
     if (n == 0) return fail(PT_E_INVALID, "no record for the session's " + std::to_string(owned_pixels(ss)) + " pixels");
     HIP_TRY(hipSetDevice(ss->dev));
-    if (const int rc = ensure_import(ss)) return rc;
-    const pt::StatesParams p = params(ss, const_cast<pt_pixel_state*>(dev_state), n);
-    // validate: every record classified and counted, every owned slot's marks checked ...
-    HIP_TRY(hipMemsetAsync(ss->state_marks, 0, kResBytes + (size_t)ss->n_slots * 4, ss->stream));
-    HIP_TRY(pt_launch_states_mark(p, ss->stream));
-    HIP_TRY(pt_launch_states_check(p, ss->stream));
+    // validate, and only then a write
     unsigned long long res[pt::SR_WORDS];
-    HIP_TRY(hipMemcpyAsync(res, p.res, sizeof(res), hipMemcpyDeviceToHost, ss->stream));
-    HIP_TRY(hipStreamSynchronize(ss->stream));
-    // ... and only then a write.  Nothing of the session has changed so far.
-    if (res[pt::SR_OUTSIDE])
-        return fail(PT_E_INVALID, std::to_string(res[pt::SR_OUTSIDE]) + " record(s) name a pixel outside the image");
-    if (res[pt::SR_BAD_RNG])
-        return fail(PT_E_INVALID, std::to_string(res[pt::SR_BAD_RNG]) + " record(s) of the session's pixels have an rng " +
-                                      "word outside 1 .. 2^31-2");
-    if (res[pt::SR_MISMARKED])
-        return fail(PT_E_INVALID, std::to_string(res[pt::SR_MISMARKED]) + " of the session's pixels are named by no " +
-                                      "record or by more than one");
+    if (const int rc = validate_import(ss, n, dev_state, res)) return rc;
+    const pt::StatesParams p = params(ss, const_cast<pt_pixel_state*>(dev_state), n);
     const uint32_t smax = (uint32_t)res[pt::SR_MAX], smin = ~(uint32_t)res[pt::SR_NMIN];
     if (smin != smax)
         return fail(PT_E_INVALID, "the records' sample counts differ (" + std::to_string(smin) + " .. " +
-                                      std::to_string(smax) + "): a session's pixels share one count");
+                                      std::to_string(smax) + "): a session's pixels share one count " +
+                                      "(pt_session_import_ragged takes them)");
     HIP_TRY(pt_launch_states_write(p, ss->stream));
+    HIP_TRY(clear_lag(ss));   // (a ragged session: uniform again)
     HIP_TRY(hipStreamSynchronize(ss->stream));
     ss->samples_done = smax;
     if (taken) *taken = res[pt::SR_TAKEN];

@@ -143,6 +143,11 @@ _sig = {
     "pt_session_import": (C.c_int, [_P, C.c_uint64, _P, C.POINTER(C.c_uint64)]),
     "pt_session_export_host": (C.c_int, [_P, _P, C.c_uint64]),
     "pt_session_import_host": (C.c_int, [_P, C.c_uint64, _P, C.POINTER(C.c_uint64)]),
+    "pt_session_trace_counts": (C.c_int, [_P, C.c_uint64, _P]),
+    "pt_session_trace_counts_host": (C.c_int, [_P, C.c_uint64, _P]),
+    "pt_session_import_ragged": (C.c_int, [_P, C.c_uint64, _P, C.POINTER(C.c_uint64)]),
+    "pt_session_import_ragged_host": (C.c_int, [_P, C.c_uint64, _P, C.POINTER(C.c_uint64)]),
+    "pt_session_samples_range": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "pt_rayq_create": (C.c_int, [_P, C.c_int, C.c_uint64, C.POINTER(_P)]),
     "pt_rayq_run": (C.c_int, [_P, _P, C.c_uint64, _P, _P]),
     "pt_rayq_stats": (C.c_int, [_P, C.POINTER(Stats)]),
@@ -171,6 +176,8 @@ _sig = {
     "pt_selftest_gamma_table": (C.c_int, [_P, _P]),
     "pt_selftest_wave_plan": (C.c_int, [_P, C.POINTER(SessionOpts), C.c_uint32, C.c_char_p, C.c_size_t]),
     "pt_selftest_state_slots": (C.c_int, [_P, C.POINTER(SessionOpts), C.c_uint64, _P, _P]),
+    "pt_selftest_count_records": (C.c_int, [_P, C.POINTER(SessionOpts), C.c_uint64, _P, C.POINTER(C.c_uint64)]),
+    "pt_selftest_count_step": (C.c_int, [C.c_uint32, C.c_uint64, _P, _P, _P, _P, C.POINTER(C.c_uint32)]),
     "pt_selftest_math": (C.c_int, [C.c_int, C.c_uint32, C.c_uint64, _P, _P]),
 }
 for _name, (_res, _args) in _sig.items():
@@ -416,6 +423,17 @@ class Scene:
         _check(_lib.pt_selftest_state_slots(self._h, C.byref(o), len(state), _ptr(state), _ptr(slots)))
         return slots
 
+    def selftest_count_records(self, rank=0, world=1, traversal=TRAVERSAL_REPLAY, window=None):
+        """Per slot of a (rank, world, window) session the record of its export -- the entry of
+        Session.trace_counts' counts -- that is the slot's pixel, -1 for a padding lane, by the
+        count kernels' own function run on the host."""
+        o = SessionOpts(0, rank, world, traversal, *(window or (0, 0, 0, 0)))
+        n = C.c_uint64()
+        _lib.pt_selftest_count_records(self._h, C.byref(o), 0, None, C.byref(n))   # (the slots; refused when > 0)
+        rec = np.zeros(n.value, np.int64)
+        _check(_lib.pt_selftest_count_records(self._h, C.byref(o), len(rec), _ptr(rec), C.byref(n)))
+        return rec
+
     def gamma_table(self):
         t = np.zeros(256, np.float32)
         _check(_lib.pt_selftest_gamma_table(self._h, _ptr(t)))
@@ -482,20 +500,47 @@ class Session:
         _check(_lib.pt_session_export_host(self._h, _ptr(state), n))
         return state
 
-    def import_states(self, state, n=None):
+    def import_states(self, state, n=None, ragged=False):
         """Replace the owned pixels by the caller's states: a numpy array of PIXEL_DTYPE, or a device
         address / an object with data_ptr() holding n records (n defaults to the object's size in
         bytes / 32).  Records of pixels that are not this session's are skipped; returns the number
-        taken.  Every owned pixel must be named once, all at one sample count (include/pt.h)."""
+        taken.  Every owned pixel must be named once, all at one sample count -- or, with
+        ragged=True, each at its own (include/pt.h)."""
         taken = C.c_uint64()
         if isinstance(state, np.ndarray):
             state = np.ascontiguousarray(state, PIXEL_DTYPE).reshape(-1)
-            _check(_lib.pt_session_import_host(self._h, len(state) if n is None else n, _ptr(state), C.byref(taken)))
+            f = _lib.pt_session_import_ragged_host if ragged else _lib.pt_session_import_host
+            _check(f(self._h, len(state) if n is None else n, _ptr(state), C.byref(taken)))
         else:
             if n is None:
                 n = state.numel() * state.element_size() // 32
-            _check(_lib.pt_session_import(self._h, n, _addr(state), C.byref(taken)))
+            f = _lib.pt_session_import_ragged if ragged else _lib.pt_session_import
+            _check(f(self._h, n, _addr(state), C.byref(taken)))
         return taken.value
+
+    def trace_counts(self, counts, n=None):
+        """Pixel i of the session, in export_states' order, takes counts[i] more samples in one pass
+        of the session's engines: a numpy array of n_pixels counts, or a device address / an object
+        with data_ptr() holding n uint32 (n defaults to n_pixels), which must not change before the
+        next sync point.  Wavefront sessions only (include/pt.h)."""
+        if isinstance(counts, np.ndarray):
+            counts = np.ascontiguousarray(counts, np.uint32).reshape(-1)
+            _check(_lib.pt_session_trace_counts_host(self._h, len(counts) if n is None else n, _ptr(counts)))
+        else:
+            _check(_lib.pt_session_trace_counts(self._h, self.n_pixels if n is None else n, _addr(counts)))
+
+    def samples_range(self):
+        """(the smallest, the largest) sample count of the session's pixels, trace() calls not yet
+        run included"""
+        lo, hi = C.c_uint32(), C.c_uint32()
+        _check(_lib.pt_session_samples_range(self._h, C.byref(lo), C.byref(hi)))
+        return lo.value, hi.value
+
+    @property
+    def ragged(self):
+        """whether the session's pixels hold different sample counts"""
+        lo, hi = self.samples_range()
+        return lo != hi
 
     def close(self):
         if getattr(self, "_h", None) and _lib is not None:
