@@ -305,6 +305,65 @@ int pt_session_import_ragged_host(pt_session* ss, uint64_t n, const pt_pixel_sta
  * included (equal: a uniform session).  Host bookkeeping: no device work, no sync point. */
 int pt_session_samples_range(const pt_session* ss, uint32_t* least, uint32_t* most);
 
+/* ------------------------------------------------------- session noise
+ * The session's own estimate of where more samples are needed, and the adaptive step it plans from
+ * it (additions to ABI 6: no existing struct or function changed).  No reference counterpart: the
+ * reference gives every pixel the same SAMPLES.  The session remembers every owned pixel's sum at an
+ * earlier count, the pixel's MARK, turns the movement of the pixel's mean since the mark into a noise
+ * figure, the figures into counts by the rule below, and runs the counts as pt_session_trace_counts
+ * runs them.  One pt_session_refine is one adaptive step; a loop of it until refined == 0 renders the
+ * frame to a noise threshold under a sample cap.
+ *   The arithmetic is f32, every operation rounded (no FMA), in this order.  A pixel now is
+ * (sum[3], k), k its own count; its mark is (M[3], a), a = 0 meaning "no mark".
+ *   No estimate -- a == 0 or k <= a:  noise = +inf (bits 0x7f800000).
+ *   Otherwise, with mean(s, n) = (1.f / float(n)) * s as pt_pixel_resolve has it:
+ *     m_c = mean(sum_c, k), p_c = mean(M_c, a)                  for c = r, g, b
+ *     d  = (|m_r - p_r| + |m_g - p_g|) + |m_b - p_b|
+ *     l  = (m_r + m_g) + m_b
+ *     lf = l > 0x1p-10f ? l : 0x1p-10f                          (a select: a NaN l takes the floor)
+ *     noise = d / sqrtf(lf)
+ * so a noise is never negative: finite, +inf or NaN (a non-finite sum).
+ *   Options: threshold, step, max_samples (0 = 2^32 - 1), spread.  Invalid: a NaN or negative
+ * threshold, step == 0, spread > 1.
+ *     hot  = noise > threshold      strict: false for NaN, true for +inf, computed or "no estimate"
+ *     hot' = hot, or with spread == 1: hot, or one of the pixel's 8 neighbours that is an owned pixel
+ *            of the SAME 16 x 16 tile is hot.  The rule never looks across a tile's border -- the
+ *            next tile may be another rank's --, so a pixel's plan does not depend on the sharding.
+ *     count = 0 if the noise is NaN; 0 if !hot'; 0 if k >= max_samples; else min(step, max_samples - k)
+ *   The result: refined = pixels with count > 0; samples = the counts' sum; unmarked = owned pixels
+ * with no estimate; nonfinite = owned pixels with a NaN noise; capped = pixels that are hot', not NaN,
+ * and stand at k >= max_samples; worst = the largest finite noise of an owned pixel that has an
+ * estimate (0: none); least, most = pt_session_samples_range after the call.
+ *   Every call first runs any trace() not yet run.  mark, noise and plan are complete on return;
+ * noise and plan change nothing of the session -- no mark, no lag, no `done` field.  Values are in
+ * pt_session_export's order; cap = room in the buffer, below pt_session_pixels: PT_E_INVALID, nothing
+ * written.  pt_session_plan's counts may be NULL (the result alone; cap is not read).
+ *   pt_session_refine is the plan, then mark := now for every pixel with count > 0, then the counts'
+ * pass (pt_session_trace_counts' own, asynchronous like it; one host read-back per step).  The counts
+ * live in the session.  refined == 0: nothing is launched and nothing changes, marks included.  A
+ * session that was never marked has no estimate anywhere: the first refine marks every pixel and gives
+ * each min(step, max_samples - k), so a loop of refine alone bootstraps itself.  A pixel with count 0
+ * keeps its mark and its state, so its noise is the same number at every later step: a pixel once cold
+ * stays cold, and refined == 0 means the frame is done.
+ *   Marks are the session's alone: pt_session_reset, pt_session_import and pt_session_import_ragged
+ * clear them all (unmarked = the pixel count afterwards), and pt_session_export does not carry them.
+ *   Refused with PT_E_INVALID, the session left exactly as it was: NULL options or result; invalid
+ * options; a buffer too small; a megakernel session, as pt_session_trace_counts refuses it.  A session
+ * that owns no pixel accepts every call and reports zeros.  No count can pass 2^32 - 1. */
+typedef struct pt_refine_opts   { float threshold; uint32_t step, max_samples, spread; } pt_refine_opts;
+typedef struct pt_refine_result { uint64_t refined, samples, unmarked, nonfinite, capped; float worst;
+                                  uint32_t least, most; } pt_refine_result;
+/* mark := now for every owned pixel */
+int pt_session_mark(pt_session* ss);
+/* every owned pixel's noise (dev_noise: a device pointer on the session's device, room for cap f32) */
+int pt_session_noise(pt_session* ss, float* dev_noise, uint64_t cap);
+int pt_session_noise_host(pt_session* ss, float* noise, uint64_t cap);
+/* the step pt_session_refine would take now: every owned pixel's count and the result */
+int pt_session_plan(pt_session* ss, const pt_refine_opts* o, uint32_t* dev_counts, uint64_t cap, pt_refine_result* res);
+int pt_session_plan_host(pt_session* ss, const pt_refine_opts* o, uint32_t* counts, uint64_t cap, pt_refine_result* res);
+/* one adaptive step */
+int pt_session_refine(pt_session* ss, const pt_refine_opts* o, pt_refine_result* res);
+
 /* ------------------------------------------------------------ ray queries
  * Scene::RayIntersection (src/scene.cpp:46-77) for the caller's own rays, bit for bit: the
  * planes, then the reference BVH with its pruning semantics (first-hit buffers, picking,
@@ -475,6 +534,15 @@ int pt_selftest_count_records(pt_scene* s, const pt_session_opts* o, uint64_t ca
  * the pass starts pixel i from, lag_after[i] = its distance below S2 afterwards.  Needs no GPU. */
 int pt_selftest_count_step(uint32_t S, uint64_t n, const uint32_t* lag, const uint32_t* counts, uint32_t* done,
                            uint32_t* lag_after, uint32_t* S2);
+/* pt_session_plan on the host ("session noise" above), for the n pixels of a session (o as
+ * pt_selftest_wave_plan takes it) in its export's order: `now` their states, `mark` their states when
+ * marked (a record with samples == 0: no mark; only sum and samples are read).  By the functions
+ * k_noise_plan runs compiled for the host, and the same in-tile neighbour rule.  noise and counts may
+ * be NULL; res->least / most = the range of now's samples.  n other than the session's pixel count,
+ * NULL or invalid options: PT_E_INVALID.  Needs no GPU. */
+int pt_selftest_refine_plan(pt_scene* s, const pt_session_opts* o, uint64_t n, const pt_pixel_state* now,
+                            const pt_pixel_state* mark, const pt_refine_opts* ro, float* noise, uint32_t* counts,
+                            pt_refine_result* res);
 /* The scalar building blocks of the device code (logf, the RNG streams, the normal and cosine
  * samplers, the Schlick term, the resolve's mean + tonemap + 8-bit step, IEEE divide / sqrt /
  * conversions), element by element: n records in, n records out (little-endian, packed).

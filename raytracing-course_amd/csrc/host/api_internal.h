@@ -18,6 +18,8 @@
 //                 and the import's classification on the host (pt_selftest_state_slots)
 //   counts.cpp    per-pixel sample counts in a session (pt_session_trace_counts / import_ragged /
 //                 samples_range), and the slot -> record map on the host (pt_selftest_count_records)
+//   noise.cpp     a session's own noise estimate and the adaptive step planned from it (pt_session_mark /
+//                 noise / plan / refine), and the plan on the host (pt_selftest_refine_plan)
 //   selftest.cpp  host execution of the device query / integrator code, and pt_selftest_math (the
 //                 device code's scalar functions on the host or in k_selftest_math) (tests only; one
 //                 hook, pt_selftest_wave_plan, is in session.cpp beside the set-up it reports)
@@ -170,6 +172,15 @@ struct DevRecords {
 uint32_t* lag_table(const pt_session* ss);
 hipError_t clear_lag(pt_session* ss);
 hipError_t launch_ragged_resolve(pt_session* ss, uint8_t* out, float* rad);
+// ... the table's making (all zero) at the first ragged call, the refusal of a megakernel session, and
+// the pass of an accepted set of counts -- their sum (above 0), the largest and the smallest count a
+// pixel stands at after them -- with its lag bookkeeping (pt_session_trace_counts, pt_session_refine)
+int ensure_lag(pt_session* ss);
+int refuse_megakernel(const pt_session* ss);
+int counts_pass(pt_session* ss, const uint32_t* dev_counts, unsigned long long sum, unsigned long long total_max,
+                unsigned long long total_min);
+// noise.cpp: every pixel's mark cleared -- no pixel has a noise estimate (no table yet: nothing to do)
+hipError_t clear_marks(pt_session* ss);
 pt::SceneView device_view(const pt_session* ss);
 pt::SceneView device_view(const pt_scene* s, const DevScene& ds);   // ... of any device copy (rayq.cpp)
 // the hand-off site named `name` (PT_HO_*: "suspend", "flush", "ringout", "exact", "side_take",
@@ -348,6 +359,10 @@ struct pt_session {
     uint32_t* counts_host_copy = nullptr;
     uint64_t lag_sum = 0;
     uint32_t lag_max = 0;
+    // the session's noise estimate (noise.cpp), an allocation of its own made at the first
+    // noise call: a plan's result block, every slot's mark (the sum and the count it held when marked;
+    // all zero: no mark), and a word per slot for a step's counts and the host forms' outputs
+    unsigned char* noise_block = nullptr;
 };
 
 // A ray-query context (rayq.cpp): the scene's copy on one device and the run state of k_rays.

@@ -15,6 +15,8 @@ namespace {
 constexpr size_t kResBytes = 256;   // the result block (CR_WORDS u64), the lag table behind it
 static_assert(pt::CR_WORDS * 8u <= kResBytes, "the counts' result block outgrew its section");
 
+}  // namespace
+
 // the lag table, made (all zero: a uniform session) at the first ragged call -- a session that makes
 // none has the arena, the set-up and the launches it always had
 int ensure_lag(pt_session* ss) {
@@ -30,6 +32,14 @@ int ensure_lag(pt_session* ss) {
     return PT_OK;
 }
 
+int refuse_megakernel(const pt_session* ss) {
+    if (ss->wave) return PT_OK;
+    return fail(PT_E_INVALID, "per-pixel sample counts need the wavefront engines: this session runs the megakernel "
+                              "(traversal EXACT or REPLAY_DIV, or PT_TUNE engine=mega), and k_trace advances by a uniform spp");
+}
+
+namespace {
+
 pt::CountsParams params(const pt_session* ss) {
     pt::CountsParams p;
     memset(&p, 0, sizeof(p));
@@ -41,12 +51,6 @@ pt::CountsParams params(const pt_session* ss) {
     p.res = reinterpret_cast<unsigned long long*>(ss->counts_block);
     p.S = p.S2 = (uint32_t)ss->samples_done;
     return p;
-}
-
-int refuse_megakernel(const pt_session* ss) {
-    if (ss->wave) return PT_OK;
-    return fail(PT_E_INVALID, "per-pixel sample counts need the wavefront engines: this session runs the megakernel "
-                              "(traversal EXACT or REPLAY_DIV, or PT_TUNE engine=mega), and k_trace advances by a uniform spp");
 }
 
 // what both forms of trace_counts refuse before they touch the device
@@ -71,6 +75,24 @@ hipError_t clear_lag(pt_session* ss) {
     ss->lag_max = 0;
     if (!ss->counts_block) return hipSuccess;
     return hipMemsetAsync(lag_table(ss), 0, (size_t)ss->n_slots * 4, ss->stream);
+}
+
+// An accepted set of counts (their sum above 0; total_max / total_min: the largest and the smallest
+// count a pixel stands at after them): every pixel's `done` at S2 - its count, the engines run them all
+// to S2 = total_max.  The lag table and the export table exist.
+int counts_pass(pt_session* ss, const uint32_t* dev_counts, unsigned long long sum, unsigned long long total_max,
+                unsigned long long total_min) {
+    if (total_max > 0xffffffffull)
+        return fail(PT_E_INVALID, "a pixel would stand at " + std::to_string(total_max) + " samples: past 2^32 - 1");
+    pt::CountsParams p = params(ss);
+    p.counts = dev_counts;
+    p.S2 = (uint32_t)total_max;
+    HIP_TRY(pt_launch_counts_bias(p, ss->stream));
+    const uint64_t owned = owned_pixels(ss), taken = owned * p.S - ss->lag_sum;   // (the pixels' samples so far)
+    if (const int rc = trace_wave(ss, p.S2 - p.S)) return rc;
+    ss->lag_sum = owned * p.S2 - (taken + sum);
+    ss->lag_max = p.S2 - (uint32_t)total_min;
+    return PT_OK;
 }
 
 hipError_t launch_ragged_resolve(pt_session* ss, uint8_t* out, float* rad) {
@@ -105,17 +127,7 @@ int pt_session_trace_counts(pt_session* ss, uint64_t n, const uint32_t* dev_coun
     HIP_TRY(hipStreamSynchronize(ss->stream));
     // ... and only then a write.  Nothing of the session has changed so far.
     if (res[pt::CR_SUM] == 0ull) return PT_OK;
-    const unsigned long long total_max = res[pt::CR_MAX_TOTAL], total_min = ~res[pt::CR_NMIN_TOTAL];
-    if (total_max > 0xffffffffull)
-        return fail(PT_E_INVALID, "a pixel would stand at " + std::to_string(total_max) + " samples: past 2^32 - 1");
-    // the pass: every pixel's `done` at S2 - its count, the engines run them all to S2
-    p.S2 = (uint32_t)total_max;
-    HIP_TRY(pt_launch_counts_bias(p, ss->stream));
-    const uint64_t owned = n, taken = owned * p.S - ss->lag_sum;   // (the pixels' samples so far)
-    if (const int rc = trace_wave(ss, p.S2 - p.S)) return rc;
-    ss->lag_sum = owned * p.S2 - (taken + res[pt::CR_SUM]);
-    ss->lag_max = p.S2 - (uint32_t)total_min;
-    return PT_OK;
+    return counts_pass(ss, dev_counts, res[pt::CR_SUM], res[pt::CR_MAX_TOTAL], ~res[pt::CR_NMIN_TOTAL]);
 }
 
 int pt_session_trace_counts_host(pt_session* ss, uint64_t n, const uint32_t* counts) {
@@ -157,6 +169,7 @@ int pt_session_import_ragged(pt_session* ss, uint64_t n, const pt_pixel_state* d
     p.S2 = smax;
     p.res = reinterpret_cast<unsigned long long*>(ss->state_marks);   // (the import's SR_* block, zeroed by the validation)
     HIP_TRY(pt_launch_counts_import(p, ss->stream));
+    HIP_TRY(clear_marks(ss));   // (new states: no noise estimate yet)
     unsigned long long lag_sum = 0;
     HIP_TRY(hipMemcpyAsync(&lag_sum, p.res + pt::SR_LAG_SUM, 8, hipMemcpyDeviceToHost, ss->stream));
     HIP_TRY(hipStreamSynchronize(ss->stream));

@@ -531,6 +531,7 @@ int pt_session_reset(pt_session* ss) {
         HIP_TRY(pt_launch_init(ip, ss->n_tiles_local, ss->stream));
     }
     HIP_TRY(clear_lag(ss));   // (a ragged session: uniform again)
+    HIP_TRY(clear_marks(ss));   // (fresh pixels: no noise estimate yet)
     ss->samples_done = 0;
     return PT_OK;
 }
@@ -597,6 +598,7 @@ void pt_session_free(pt_session* ss) {
     (void)hipFree(ss->rad); (void)hipFree(ss->wg_prof);
     (void)hipFree(ss->state_tile_rec); (void)hipFree(ss->state_marks);
     (void)hipFree(ss->counts_block); (void)hipFree(ss->counts_host_copy);
+    (void)hipFree(ss->noise_block);
     if (ss->ctl_host) (void)hipHostFree(ss->ctl_host);
     if (ss->prog_host) (void)hipHostFree(ss->prog_host);
     if (ss->side_taken) (void)hipEventDestroy(ss->side_taken);

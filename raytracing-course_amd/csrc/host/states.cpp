@@ -153,6 +153,7 @@ int pt_session_import(pt_session* ss, uint64_t n, const pt_pixel_state* dev_stat
                                       "(pt_session_import_ragged takes them)");
     HIP_TRY(pt_launch_states_write(p, ss->stream));
     HIP_TRY(clear_lag(ss));   // (a ragged session: uniform again)
+    HIP_TRY(clear_marks(ss));   // (new states: no noise estimate yet)
     HIP_TRY(hipStreamSynchronize(ss->stream));
     ss->samples_done = smax;
     if (taken) *taken = res[pt::SR_TAKEN];

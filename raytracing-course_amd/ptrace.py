@@ -112,6 +112,18 @@ class SessionOpts(C.Structure):
                 ("win_x0", C.c_uint32), ("win_y0", C.c_uint32), ("win_w", C.c_uint32), ("win_h", C.c_uint32)]
 
 
+class RefineOpts(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("step", C.c_uint32), ("max_samples", C.c_uint32), ("spread", C.c_uint32)]
+
+
+class RefineResult(C.Structure):
+    _fields_ = [("refined", C.c_uint64), ("samples", C.c_uint64), ("unmarked", C.c_uint64), ("nonfinite", C.c_uint64),
+                ("capped", C.c_uint64), ("worst", C.c_float), ("least", C.c_uint32), ("most", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _P = C.c_void_p
 _sig = {
     "pt_scene_load": (C.c_int, [C.c_char_p, C.POINTER(_P)]),
@@ -148,6 +160,12 @@ _sig = {
     "pt_session_import_ragged": (C.c_int, [_P, C.c_uint64, _P, C.POINTER(C.c_uint64)]),
     "pt_session_import_ragged_host": (C.c_int, [_P, C.c_uint64, _P, C.POINTER(C.c_uint64)]),
     "pt_session_samples_range": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "pt_session_mark": (C.c_int, [_P]),
+    "pt_session_noise": (C.c_int, [_P, _P, C.c_uint64]),
+    "pt_session_noise_host": (C.c_int, [_P, _P, C.c_uint64]),
+    "pt_session_plan": (C.c_int, [_P, C.POINTER(RefineOpts), _P, C.c_uint64, C.POINTER(RefineResult)]),
+    "pt_session_plan_host": (C.c_int, [_P, C.POINTER(RefineOpts), _P, C.c_uint64, C.POINTER(RefineResult)]),
+    "pt_session_refine": (C.c_int, [_P, C.POINTER(RefineOpts), C.POINTER(RefineResult)]),
     "pt_rayq_create": (C.c_int, [_P, C.c_int, C.c_uint64, C.POINTER(_P)]),
     "pt_rayq_run": (C.c_int, [_P, _P, C.c_uint64, _P, _P]),
     "pt_rayq_stats": (C.c_int, [_P, C.POINTER(Stats)]),
@@ -178,6 +196,8 @@ _sig = {
     "pt_selftest_state_slots": (C.c_int, [_P, C.POINTER(SessionOpts), C.c_uint64, _P, _P]),
     "pt_selftest_count_records": (C.c_int, [_P, C.POINTER(SessionOpts), C.c_uint64, _P, C.POINTER(C.c_uint64)]),
     "pt_selftest_count_step": (C.c_int, [C.c_uint32, C.c_uint64, _P, _P, _P, _P, C.POINTER(C.c_uint32)]),
+    "pt_selftest_refine_plan": (C.c_int, [_P, C.POINTER(SessionOpts), C.c_uint64, _P, _P, C.POINTER(RefineOpts), _P, _P,
+                                          C.POINTER(RefineResult)]),
     "pt_selftest_math": (C.c_int, [C.c_int, C.c_uint32, C.c_uint64, _P, _P]),
 }
 for _name, (_res, _args) in _sig.items():
@@ -434,6 +454,22 @@ class Scene:
         _check(_lib.pt_selftest_count_records(self._h, C.byref(o), len(rec), _ptr(rec), C.byref(n)))
         return rec
 
+    def selftest_refine_plan(self, now, mark, threshold, step, max_samples=0, spread=0, rank=0, world=1,
+                             traversal=TRAVERSAL_REPLAY, window=None):
+        """Session.plan on the host for a (rank, world, window) session whose pixels hold the states
+        `now` and were marked at the states `mark` (export order; a mark with samples == 0: no mark),
+        by the plan kernel's own functions: returns (noise, counts, result dict)."""
+        now = np.ascontiguousarray(now, PIXEL_DTYPE).reshape(-1)
+        mark = np.ascontiguousarray(mark, PIXEL_DTYPE).reshape(-1)
+        if len(now) != len(mark):
+            raise ValueError("one mark per state")
+        o = SessionOpts(0, rank, world, traversal, *(window or (0, 0, 0, 0)))
+        ro, res = RefineOpts(threshold, step, max_samples, spread), RefineResult()
+        noise, counts = np.zeros(len(now), np.float32), np.zeros(len(now), np.uint32)
+        _check(_lib.pt_selftest_refine_plan(self._h, C.byref(o), len(now), _ptr(now), _ptr(mark), C.byref(ro),
+                                            _ptr(noise), _ptr(counts), C.byref(res)))
+        return noise, counts, res.as_dict()
+
     def gamma_table(self):
         t = np.zeros(256, np.float32)
         _check(_lib.pt_selftest_gamma_table(self._h, _ptr(t)))
@@ -541,6 +577,43 @@ class Session:
         """whether the session's pixels hold different sample counts"""
         lo, hi = self.samples_range()
         return lo != hi
+
+    def mark(self):
+        """Remember every owned pixel's sum and count: the state its noise is measured against
+        (include/pt.h "session noise").  Wavefront sessions only, as every noise call."""
+        _check(_lib.pt_session_mark(self._h))
+
+    def noise(self, dev=None):
+        """Every owned pixel's noise since its mark, in export_states' order (+inf: no estimate): a
+        float32 array, or with `dev` -- a device address or an object with data_ptr(), room for
+        n_pixels float32 -- a fill of it (returns dev)."""
+        n = self.n_pixels
+        if dev is not None:
+            _check(_lib.pt_session_noise(self._h, _addr(dev), n))
+            return dev
+        out = np.zeros(n, np.float32)
+        _check(_lib.pt_session_noise_host(self._h, _ptr(out), n))
+        return out
+
+    def plan(self, threshold, step, max_samples=0, spread=0, dev=None):
+        """The step refine() would take now, nothing of the session changed: (counts, result dict), the
+        counts a uint32 array in export_states' order, or `dev` filled (room for n_pixels uint32)."""
+        n = self.n_pixels
+        o, res = RefineOpts(threshold, step, max_samples, spread), RefineResult()
+        if dev is not None:
+            _check(_lib.pt_session_plan(self._h, C.byref(o), _addr(dev), n, C.byref(res)))
+            return dev, res.as_dict()
+        counts = np.zeros(n, np.uint32)
+        _check(_lib.pt_session_plan_host(self._h, C.byref(o), _ptr(counts), n, C.byref(res)))
+        return counts, res.as_dict()
+
+    def refine(self, threshold, step, max_samples=0, spread=0):
+        """One adaptive step: every pixel whose noise is above the threshold (with spread=1 also its
+        neighbours inside its tile) is marked and takes min(step, max_samples - its count) samples in
+        one pass of the session's engines.  Returns the result dict; "refined" == 0: the frame is done."""
+        o, res = RefineOpts(threshold, step, max_samples, spread), RefineResult()
+        _check(_lib.pt_session_refine(self._h, C.byref(o), C.byref(res)))
+        return res.as_dict()
 
     def close(self):
         if getattr(self, "_h", None) and _lib is not None:
