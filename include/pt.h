@@ -486,6 +486,70 @@ int pt_sample_pixels(pt_scene* s, int device, uint64_t n, pt_pixel_state* state,
  * uses.  Either output may be NULL.  A state with samples == 0: PT_E_INVALID. */
 int pt_pixel_resolve(pt_scene* s, uint64_t n, const pt_pixel_state* state, float* mean, uint8_t* rgb);
 
+/* ------------------------------------------------------------ first-hit features
+ * What a position on the image plane looks at (additions to ABI 6: no existing struct or function
+ * changed): the closest hit of the camera's ray through it, and the scene data of the primitive
+ * that hit names -- albedo, normal and depth buffers for a filter or denoiser, a cost map,
+ * picking, a G-buffer preview.  No reference counterpart as an interface.  A position is two
+ * floats (x, y) in pixel units, used as given, exactly as pt_camera_rays takes them; it may lie
+ * outside the frame and may be non-finite.  Its record is defined by the reference:
+ *   ray = Camera::GetToRay(x, y)              (src/scene.cpp:180-187; the direction not normalised)
+ *   hit = Scene::RayIntersection(ray)         (src/scene.cpp:46-77)
+ * and everything else is a copy of primitives[hit.id]'s data, or of the scene's BG_COLOR: no
+ * arithmetic is added, so every field agrees with the reference's bit for bit.  On a miss id = -1,
+ * emission = BG_COLOR -- what RayTrace returns for that ray -- and every other word is 0.  A
+ * non-finite position gives a non-finite ray, which is answered as the reference answers it. */
+typedef struct pt_feature {          /* 64 B; arrays 16-byte aligned */
+    int32_t  id;                     /* bytes 0..23: the pt_ray_hit of `ray`, byte for byte */
+    float    t;
+    float    n[3];
+    uint32_t interior;
+    float    albedo[3];              /* primitives[id].col */
+    float    ior;                    /* primitives[id].ior, whatever the material */
+    float    emission[3];            /* primitives[id].emission; on a miss: BG_COLOR */
+    uint32_t material;               /* 0 diffuse, 1 metallic, 2 dielectric */
+    uint32_t type;                   /* 1 plane, 2 box, 4 ellipsoid, 8 triangle; 0 = miss */
+    uint32_t reserved;               /* written 0 */
+} pt_feature;
+typedef struct pt_featq pt_featq;
+
+/* a feature context on `device` for runs of up to max_points (1 .. 2^32 - 1) positions; prepares
+ * the scene if needed; the scene must outlive the context.  The camera is read here.  The context
+ * holds 4 B of device memory per point. */
+int pt_featq_create(pt_scene* s, int device, uint64_t max_points, pt_featq** out);
+/* asynchronous on `stream` (a hipStream_t; NULL = the null stream); dev_xy (2 floats per point,
+ * 8-byte aligned) and dev_out (16-byte aligned) are device pointers on the context's device;
+ * n <= max_points; n = 0 enqueues nothing; a refusal writes nothing.  One run at a time per
+ * context: a run first waits (on the host) for the context's previous run. */
+int pt_featq_run(pt_featq* q, void* stream, uint64_t n, const float* dev_xy, pt_feature* dev_out);
+/* waits for the last run; fills what pt_rayq_stats fills (rays = the points) for the runs since
+ * the last call; errors must be 0 */
+int pt_featq_stats(pt_featq* q, pt_stats* st);
+void pt_featq_free(pt_featq* q);
+/* convenience, host pointers: uploads, runs, downloads, in chunks of at most 2^22 points so that
+ * device memory stays bounded; synchronous; stats may be NULL */
+int pt_features(pt_scene* s, int device, uint64_t n, const float* xy, pt_feature* out, pt_stats* stats);
+
+/* One record per pixel the session owns, in pt_session_export's order, for the pixel's centre
+ * (float(x) + 0.5f, float(y) + 0.5f), x and y the image's global coordinates.  dev_out: a 16-byte
+ * aligned device pointer with room for cap records; cap below pt_session_pixels: PT_E_INVALID,
+ * nothing written (a session that owns no pixel accepts cap = 0).  Complete on return.  Works for
+ * a session of any traversal or engine.  Reads nothing of the pixels' states and changes nothing
+ * of the session: trace() calls not yet run stay pending, marks, lag and pt_session_stats are
+ * untouched; the call's work is reported through st alone (as pt_featq_stats fills it; may be
+ * NULL).  What the session needs for this -- a feature context and 8 B per owned pixel -- is made
+ * at the first call. */
+int pt_session_features(pt_session* ss, pt_feature* dev_out, uint64_t cap, pt_stats* st);
+int pt_session_features_host(pt_session* ss, pt_feature* out, uint64_t cap, pt_stats* st);
+
+/* Host only, after pt_scene_prepare: the scene data a hit's id names, for every primitive in the
+ * prepared order (pt_scene_dump_bvh's); n must equal pt_scene_info.n_prims.  With it the id of any
+ * pt_ray_hit or pt_feature resolves on the host. */
+typedef struct pt_prim_shade { float albedo[3]; float ior; float emission[3]; uint32_t material; } pt_prim_shade;
+int pt_scene_shade(const pt_scene* s, pt_prim_shade* out, size_t n);
+/* Host only: the scene's BG_COLOR */
+int pt_scene_background(const pt_scene* s, float rgb[3]);
+
 const char* pt_last_error(void);
 int pt_abi_version(void);
 
@@ -508,6 +572,10 @@ int pt_selftest_paths_host(pt_scene* s, uint64_t n, const pt_path_ray* in, pt_pa
  * added are the counts' sum.  Needs no GPU. */
 int pt_selftest_pixels_host(pt_scene* s, uint64_t n, pt_pixel_state* state, const uint32_t* counts, uint32_t spp,
                             uint64_t* counters8);
+/* n feature records on the host, as pt_featq_run writes them: camera_ray, the query state machine
+ * run to completion, then the shade lookup, by the inline functions k_feats runs.  counters8 as
+ * pt_selftest_paths_host fills it (rays = n); may be NULL.  Needs no GPU. */
+int pt_selftest_features_host(pt_scene* s, uint64_t n, const float* xy, pt_feature* out, uint64_t* counters8);
 /* the 256-entry gamma threshold table used by the device tonemap */
 int pt_selftest_gamma_table(const pt_scene* s, float* thr256);
 /* session set-up without a device: the geometry (o's rank, world, window, traversal; o->device is

@@ -1,6 +1,12 @@
 // pt_rays.h -- the ray-query engine's parameter block (pt_rays.hip, host/rayq.cpp): closest-hit
 // queries (Scene::RayIntersection, src/scene.cpp:46-77) for rays the caller supplies -- no pixels,
 // no chains, no shading.  DESIGN.md §4.5.
+//
+// The engine itself -- the persistent refill loop, its service step, the exact list and the
+// per-wave counter flush -- is a template over a job type (rays_engine / rays_exact_engine below,
+// device compiles only), so that an engine with another source of rays and another record per item
+// instantiates it and does not copy it: pt_rays.hip with the caller's rays and 24-B hits,
+// pt_feats.hip with the camera's rays and 64-B first-hit features.
 #pragma once
 #include "pt_kernels.h"
 
@@ -39,3 +45,159 @@ struct RaysParams {
 // workgroup (a multiple of 64 whose stacks fit the workgroup's LDS); e0 / e1 around the two kernels
 hipError_t pt_launch_rays(const pt::RaysParams& p, uint32_t grid, uint32_t block, hipStream_t s, hipEvent_t e0,
                           hipEvent_t e1);
+
+#if defined(__HIPCC__)
+// ---- the engine (device code) ----------------------------------------------------------------
+// PARAMS: a parameter block with RaysParams' run members (S, n, batch, service, head, exact_n,
+// exact, counters, aux_words, dfs_words).  JOB: what an item is --
+//   Ray  ray(size_t i) const                             the ray of item i
+//   void store(size_t i, int id, const Hit& h) const     item i's record from its closest hit (id < 0: a miss,
+//                                                        h then holds nothing)
+#include "pt_devutil.h"
+
+namespace pt {
+
+// the statistics a wave gathered, flushed once (one atomic per counter and wave)
+struct RayStats {
+    QCounts C{0u, 0u, 0u, 0u};
+    uint32_t rays = 0u, err = 0u, exact = 0u, exact_ray = 0u;
+    __device__ __forceinline__ void flush(unsigned long long* counters) const {
+        unsigned long long* ctr = ctr_copy(counters);
+        wave_add_u64(ctr + CTR_RAYS, rays);
+        wave_add_u64(ctr + CTR_NODES, C.nodes);
+        wave_add_u64(ctr + CTR_PTESTS, C.ptests);
+        wave_add_u64(ctr + CTR_PLANES, C.planes);
+        wave_add_u64(ctr + CTR_ERRORS, err);
+        wave_add_u64(ctr + CTR_AUX, C.aux);
+        wave_add_u64(ctr + CTR_FALLBACKS, exact);
+        wave_add_u64(ctr + CTR_FALLBACKS_RAY, exact_ray);
+    }
+};
+
+// a lane takes item i: the planes, then the BVH query's set-up
+template <class PARAMS, class JOB>
+__device__ __forceinline__ void take_ray(const PARAMS& P, const JOB& job, size_t i, Query& q, RayStats& st) {
+    const Ray ray = job.ray(i);
+    float pt;
+    int pid;
+    q_planes(P.S, ray, pt, pid);
+    st.C.planes += P.S.n_planes;
+    q_init(P.S, ray, pt, pid, q);
+    st.rays++;
+    if (q.phase == Q_EXACT) st.exact_ray++;   // a non-finite ray: the exact DFS by design
+}
+
+// A query that left Q_AUX / Q_REPLAY retires (every lane of the wave calls this; `fin` = this lane
+// retires item i): a Q_EXACT ray joins the exact list, any other one stores its record, the hit
+// recomputed from its primitive exactly as q_run does (the probe computes t only).
+template <class PARAMS, class JOB>
+__device__ __forceinline__ void retire(const PARAMS& P, const JOB& job, bool fin, size_t i, const Query& q,
+                                       RayStats& st) {
+    const bool ex = fin && q.phase == Q_EXACT;
+    const uint32_t k = wave_append(P.exact_n, ex);
+    if (ex) {
+        P.exact[k] = (uint32_t)i;
+        st.exact++;
+    } else if (fin) {
+        Hit h;
+        if (q.res_id >= 0) {
+            const bool ok = prim_intersect(P.S.prims[q.res_id], q.ray, h);
+            if (!ok || f2u(h.t) != f2u(q.res_t)) st.err++;   // must never happen (the tests check)
+        }
+        job.store(i, q.res_id, h);
+    }
+}
+
+// a lane per item, with refill: persistent waves, every trip advances each running lane by one
+// q_step; once enough lanes have finished, they retire and take the next items.  The workgroup's
+// dynamic LDS: (blockDim.x / 64) x 64 x (aux_words + 1) words.
+template <class PARAMS, class JOB>
+__device__ __forceinline__ void rays_engine(const PARAMS& P, const JOB& job) {
+    extern __shared__ uint32_t lds_stack[];
+    const uint32_t lane = threadIdx.x & 63u;
+    // [word][lane] per wave: words 0 .. aux_words - 1, then the trash word
+    LdsMemN<64u> stk{lds_stack + (threadIdx.x >> 6) * 64u * (P.aux_words + 1u) + lane, P.aux_words, P.aux_words};
+    RayStats st;
+    Query q;
+    q.phase = Q_DONE;
+    bool have = false;        // this lane holds a ray that has not retired
+    size_t idx = 0;
+    // the wave's reservation [rnext, rnext + rleft) of item indices, and whether the work counter may
+    // still be below n (all three wave-uniform)
+    unsigned long long rnext = 0ull;
+    uint32_t rleft = 0u;
+    bool more = true;
+    // Why this loop ends, from the wave's own state alone (it waits for no other wave or workgroup
+    // anywhere: the only shared words are the work counter and the exact list's count, both only
+    // ever added to):
+    //   * a pull adds `batch` >= 64 to the work counter, so after at most n / batch + 1 pulls by
+    //     all waves together every pull returns a value >= n and `more` turns false for good;
+    //   * a lane that holds a ray advances by one q_step per trip, and a query takes a finite
+    //     number of steps (the state machine q_run loops over);
+    //   * a trip on which no lane runs is a service step, which retires every finished lane, so
+    //     it either hands out items (the reservation shrinks, or a pull moves the counter on) or
+    //     finds nothing left and leaves;
+    //   * so the trips are bounded by the pulls, plus the steps of the rays the wave took.
+    for (;;) {
+        const bool run = have && (q.phase == Q_AUX || q.phase == Q_REPLAY);
+        const unsigned long long mrun = __ballot(run);
+        // The service step, once `service` lanes wait (finished or empty) or none runs: the finished
+        // lanes retire and the empty ones take items.  Not on every trip: a retiring lane recomputes
+        // its hit and a taking one tests the planes, each behind dependent loads that the whole
+        // wave waits for -- a few lanes at a time, that cost as much as the trip's q_step.
+        if (64u - (uint32_t)__popcll(mrun) >= P.service || mrun == 0ull) {
+            const bool fin = have && !run;
+            retire(P, job, fin, idx, q, st);
+            if (fin) have = false;
+            if (rleft == 0u && more) {
+                // one atomic per pull, by one lane, for the whole wave
+                unsigned long long got = 0ull;
+                if (lane == 0u) got = atomicAdd(P.head, (unsigned long long)P.batch);
+                // (lane 0's value in scalar registers: the reservation is wave-uniform)
+                const unsigned long long base =
+                    (unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(got >> 32)) << 32 |
+                    __builtin_amdgcn_readfirstlane((uint32_t)got);
+                rnext = base;
+                rleft = base < P.n ? (uint32_t)(P.n - base < P.batch ? P.n - base : P.batch) : 0u;
+                more = base + P.batch < P.n;
+            }
+            if (rleft != 0u) {
+                const unsigned long long m = __ballot(!have);
+                const uint32_t k = lanes_below(m);
+                if (!have && k < rleft) {
+                    idx = (size_t)(rnext + k);
+                    take_ray(P, job, idx, q, st);
+                    have = true;
+                }
+                const uint32_t took = (uint32_t)__popcll(m) < rleft ? (uint32_t)__popcll(m) : rleft;
+                rnext += took;
+                rleft -= took;
+            }
+            if (rleft == 0u && !more && __ballot(have) == 0ull) break;
+        }
+        if (have && (q.phase == Q_AUX || q.phase == Q_REPLAY)) q_step(P.S, q, st.C, stk);
+    }
+    st.flush(P.counters);
+}
+
+// The exact list's items (k_wexact's shape: 64-lane workgroups, grid-stride, the DFS stack in LDS:
+// 64 x (dfs_words + 1) words); launched after every run of rays_engine, its count read from device memory
+template <class PARAMS, class JOB>
+__device__ __forceinline__ void rays_exact_engine(const PARAMS& P, const JOB& job) {
+    extern __shared__ uint32_t lds_stack[];
+    const uint32_t n = *P.exact_n;
+    LdsMemN<64u> stk{lds_stack + threadIdx.x, P.dfs_words, P.dfs_words};
+    RayStats st;
+    for (uint32_t k = blockIdx.x * 64u + threadIdx.x; k < n; k += gridDim.x * 64u) {
+        const size_t i = P.exact[k];
+        const Ray ray = job.ray(i);
+        Hit h;
+        const int id = q_exact(P.S, ray, stk, h, st.C);
+        job.store(i, id, h);
+    }
+    st.C.planes = 0u;   // (the refill loop counted these rays' plane tests when it took them)
+    st.flush(P.counters);
+}
+
+}  // namespace pt
+#endif  // __HIPCC__

@@ -10,6 +10,9 @@
 //   rounds.cpp    the wavefront pass: path rounds, early / final cooperative launches
 //   render.cpp    Scene::Render equivalent: per-GPU threads, the RCCL / host gather, PPM
 //   rayq.cpp      the ray-query engine: closest-hit queries for the caller's rays (pt_rayq_*, pt_intersect)
+//   featq.cpp     the first-hit feature engine: the closest hit and the hit primitive's scene data for the
+//                 caller's image-plane positions, and for a session's pixel centres (pt_featq_*, pt_features,
+//                 pt_session_features)
 //   pathq.cpp     the batch radiance engine: RayTrace for the caller's rays (pt_pathq_*, pt_radiance,
 //                 pt_camera_rays)
 //   pixq.cpp      the pixel-sample engine: Sample's loop for the caller's pixel states (pt_pixq_*,
@@ -43,6 +46,7 @@
 #include <vector>
 
 #include "../device/pt_coop.h"
+#include "../device/pt_feats.h"
 #include "../device/pt_kernels.h"
 #include "../device/pt_paths.h"
 #include "../device/pt_pixels.h"
@@ -363,6 +367,10 @@ struct pt_session {
     // noise call: a plan's result block, every slot's mark (the sum and the count it held when marked;
     // all zero: no mark), and a word per slot for a step's counts and the host forms' outputs
     unsigned char* noise_block = nullptr;
+    // first-hit features (featq.cpp), made at the first pt_session_features: a feature
+    // context of the session's scene and device for its owned pixels, and their centres in the export's order
+    pt_featq* feat_q = nullptr;
+    pt::FeatXY* feat_xy = nullptr;
 };
 
 // A ray-query context (rayq.cpp): the scene's copy on one device and the run state of k_rays.
@@ -378,6 +386,22 @@ struct pt_rayq {
     bool pending = false;           // ... whose time has not been added to kernel_ms yet
     double kernel_ms = 0.0;         // since the last pt_rayq_stats
     unsigned long long seen[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the counters at the last pt_rayq_stats
+};
+
+// A first-hit feature context (featq.cpp): the scene's copy on one device and the run state of k_feats.
+struct pt_featq {
+    pt_scene* sc = nullptr;
+    int dev = 0;
+    uint64_t max_points = 0;
+    pt::FeatsParams p{};            // the view of the device copy, the camera and the arena's pieces (xy, out, n, batch:
+                                    // per run)
+    // one allocation: the control block | the statistics counters | the exact list (max_points words)
+    unsigned char* arena = nullptr;
+    uint32_t block = 256, max_grid = 1;   // k_feats' workgroup (its lanes' stacks fit the LDS) and the resident grid
+    hipEvent_t e0 = nullptr, e1 = nullptr;   // around the last run's kernels
+    bool pending = false;           // ... whose time has not been added to kernel_ms yet
+    double kernel_ms = 0.0;         // since the last pt_featq_stats
+    unsigned long long seen[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the counters at the last pt_featq_stats
 };
 
 // A batch radiance context (pathq.cpp): the scene's copy on one device and the run state of k_paths.

@@ -585,6 +585,27 @@ int pt_scene_dump_bvh(const pt_scene* s, void* nodes_out, size_t nodes_bytes, vo
     return PT_OK;
 }
 
+static_assert(sizeof(pt_prim_shade) == sizeof(pt::Shade) && sizeof(pt_prim_shade) == 32 && offsetof(pt_prim_shade, ior) == 12 &&
+                  offsetof(pt_prim_shade, emission) == 16 && offsetof(pt_prim_shade, material) == 28,
+              "shading record: ABI and device layouts differ");
+
+// the kernels' shading records (build_device_layout), which a pt_prim_shade is word for word
+int pt_scene_shade(const pt_scene* s, pt_prim_shade* out, size_t n) {
+    if (!s || !s->prepared) return fail(PT_E_INVALID, "scene not prepared");
+    if (n != s->dshade.size()) return fail(PT_E_INVALID, "room for " + std::to_string(n) + " records, the scene has " +
+                                                            std::to_string(s->dshade.size()) + " primitives");
+    if (n == 0) return PT_OK;
+    if (!out) return fail(PT_E_INVALID, "null shading buffer");
+    memcpy(out, s->dshade.data(), n * sizeof(pt_prim_shade));
+    return PT_OK;
+}
+
+int pt_scene_background(const pt_scene* s, float rgb[3]) {
+    if (!s || !rgb) return fail(PT_E_INVALID, "null argument");
+    memcpy(rgb, s->hs.bg, 3 * sizeof(float));
+    return PT_OK;
+}
+
 void pt_scene_free(pt_scene* s) {
     if (!s) return;
     for (auto& kv : s->dev) {

@@ -243,6 +243,37 @@ int pt_selftest_pixels_host(pt_scene* s, uint64_t n, pt_pixel_state* state, cons
     return C.errs ? fail(PT_E_INVALID, "recomputed closest hit differs from the query's") : PT_OK;
 }
 
+int pt_selftest_features_host(pt_scene* s, uint64_t n, const float* xy, pt_feature* out, uint64_t* counters8) {
+    if (!s) return fail(PT_E_INVALID, "null scene");
+    if (n > 0 && (!xy || !out)) return fail(PT_E_INVALID, "null position or feature buffer");
+    int rc = pt_scene_prepare(s);
+    if (rc) return rc;
+    const pt::SceneView V = host_view(s, PT_TRAVERSAL_REPLAY);
+    const pt::CamView cam = make_cam(s);
+    HostStack stk;
+    uint64_t c[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // (slots CTR_RAYS .. CTR_FALLBACKS_RAY)
+    for (uint64_t i = 0; i < n; ++i) {
+        // k_feats' job on one thread: the position's ray, the query state machine run to completion
+        // (as pt_selftest_ray_intersection runs it), the record from the hit
+        const pt::Ray ray = pt::camera_ray(cam, xy[2 * i], xy[2 * i + 1]);
+        pt::QCounts Q{0u, 0u, 0u, 0u};
+        uint32_t ex = 0;
+        pt::Hit h;
+        const int id = pt::q_run(V, ray, stk, h, Q, ex);
+        if (Q.planes & 0x80000000u) c[pt::CTR_ERRORS]++;   // recomputed hit differs
+        const float w = pt::q_prep(V, ray).w;
+        if (w != w) c[pt::CTR_FALLBACKS_RAY]++;   // a non-finite ray (q_init_pre: Q_EXACT from the start)
+        c[pt::CTR_RAYS]++;
+        c[pt::CTR_NODES] += Q.nodes; c[pt::CTR_PTESTS] += Q.ptests; c[pt::CTR_PLANES] += Q.planes & 0x7fffffffu;
+        c[pt::CTR_AUX] += Q.aux; c[pt::CTR_FALLBACKS] += ex;
+        pt::Feature f;
+        pt::feature_fill(V, id, h, f);
+        memcpy(out + i, &f, sizeof(f));
+    }
+    if (counters8) memcpy(counters8, c, sizeof(c));
+    return c[pt::CTR_ERRORS] ? fail(PT_E_INVALID, "recomputed closest hit differs from the query's") : PT_OK;
+}
+
 int pt_selftest_gamma_table(const pt_scene* s, float* thr256) {
     if (!s || !s->prepared || !thr256) return fail(PT_E_INVALID, "scene not prepared");
     memcpy(thr256, s->thr, sizeof(s->thr));

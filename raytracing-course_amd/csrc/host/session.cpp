@@ -599,6 +599,8 @@ void pt_session_free(pt_session* ss) {
     (void)hipFree(ss->state_tile_rec); (void)hipFree(ss->state_marks);
     (void)hipFree(ss->counts_block); (void)hipFree(ss->counts_host_copy);
     (void)hipFree(ss->noise_block);
+    pt_featq_free(ss->feat_q);
+    (void)hipFree(ss->feat_xy);
     if (ss->ctl_host) (void)hipHostFree(ss->ctl_host);
     if (ss->prog_host) (void)hipHostFree(ss->prog_host);
     if (ss->side_taken) (void)hipEventDestroy(ss->side_taken);

@@ -43,6 +43,13 @@ PATHS_CHUNK = 1 << 22   # pt_radiance moves the paths in chunks of at most this 
 # normal_distribution's saved value; sum / samples = Scene::Sample's summary and its loop counter
 PIXEL_DTYPE = np.dtype([("rng", np.uint32), ("saved", np.float32), ("x", np.uint32), ("y", np.uint32),
                         ("sum", np.float32, (3,)), ("samples", np.uint32)])
+# pt_feature / pt_prim_shade (include/pt.h "first-hit features")
+FEATURE_DTYPE = np.dtype([("id", np.int32), ("t", np.float32), ("n", np.float32, (3,)), ("interior", np.uint32),
+                          ("albedo", np.float32, (3,)), ("ior", np.float32), ("emission", np.float32, (3,)),
+                          ("material", np.uint32), ("type", np.uint32), ("reserved", np.uint32)])
+SHADE_DTYPE = np.dtype([("albedo", np.float32, (3,)), ("ior", np.float32), ("emission", np.float32, (3,)),
+                        ("material", np.uint32)])
+FEATS_CHUNK = 1 << 22    # pt_features moves the points in chunks of at most this many
 PIXELS_CHUNK = 1 << 22   # pt_sample_pixels moves the records in chunks of at most this many
 # pt_selftest_math's ops (include/pt.h PT_MATH_*): name -> (op, record in, record out; None = 3n f32)
 _VECS = np.dtype([("v", np.float32, (8, 3))])
@@ -184,6 +191,15 @@ _sig = {
     "pt_pixq_free": (None, [_P]),
     "pt_sample_pixels": (C.c_int, [_P, C.c_int, C.c_uint64, _P, _P, C.c_uint32, C.POINTER(Stats)]),
     "pt_pixel_resolve": (C.c_int, [_P, C.c_uint64, _P, _P, _P]),
+    "pt_featq_create": (C.c_int, [_P, C.c_int, C.c_uint64, C.POINTER(_P)]),
+    "pt_featq_run": (C.c_int, [_P, _P, C.c_uint64, _P, _P]),
+    "pt_featq_stats": (C.c_int, [_P, C.POINTER(Stats)]),
+    "pt_featq_free": (None, [_P]),
+    "pt_features": (C.c_int, [_P, C.c_int, C.c_uint64, _P, _P, C.POINTER(Stats)]),
+    "pt_session_features": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(Stats)]),
+    "pt_session_features_host": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(Stats)]),
+    "pt_scene_shade": (C.c_int, [_P, _P, C.c_size_t]),
+    "pt_scene_background": (C.c_int, [_P, _P]),
     "pt_last_error": (C.c_char_p, []),
     "pt_abi_version": (C.c_int, []),
     "pt_selftest_ray_intersection": (C.c_int, [_P, C.c_int32, C.c_uint32, _P, _P, _P, _P]),
@@ -191,6 +207,7 @@ _sig = {
                                           C.c_uint32, _P]),
     "pt_selftest_paths_host": (C.c_int, [_P, C.c_uint64, _P, _P, _P]),
     "pt_selftest_pixels_host": (C.c_int, [_P, C.c_uint64, _P, _P, C.c_uint32, _P]),
+    "pt_selftest_features_host": (C.c_int, [_P, C.c_uint64, _P, _P, _P]),
     "pt_selftest_gamma_table": (C.c_int, [_P, _P]),
     "pt_selftest_wave_plan": (C.c_int, [_P, C.POINTER(SessionOpts), C.c_uint32, C.c_char_p, C.c_size_t]),
     "pt_selftest_state_slots": (C.c_int, [_P, C.POINTER(SessionOpts), C.c_uint64, _P, _P]),
@@ -340,6 +357,32 @@ class Scene:
         _check(_lib.pt_camera_rays(self._h, len(xy), _ptr(xy), _ptr(rays)))
         return rays
 
+    def features(self, xy, device=0):
+        """First-hit features on the GPU: `xy` reshapes to (n, 2) float32 image-plane positions in
+        pixel units (used as given; outside the frame and non-finite allowed).  Returns (records,
+        stats): records is an array of FEATURE_DTYPE -- the closest hit of Camera::GetToRay(x, y),
+        then the hit primitive's albedo, ior, emission, material and type; a miss is id = -1 with
+        emission = BG_COLOR and every other word 0."""
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        out = np.zeros(len(xy), FEATURE_DTYPE)
+        st = Stats()
+        _check(_lib.pt_features(self._h, device, len(xy), _ptr(xy), _ptr(out), C.byref(st)))
+        return out, st.as_dict()
+
+    def shade(self):
+        """Every primitive's albedo, ior, emission and material (an array of SHADE_DTYPE) in the
+        prepared order: what the id of a hit or a feature record names.  After prepare()."""
+        out = np.zeros(self.info["n_prims"], SHADE_DTYPE)
+        _check(_lib.pt_scene_shade(self._h, _ptr(out), len(out)))
+        return out
+
+    @property
+    def background(self):
+        """the scene's BG_COLOR, 3 float32"""
+        rgb = np.zeros(3, np.float32)
+        _check(_lib.pt_scene_background(self._h, _ptr(rgb)))
+        return rgb
+
     def pixel_init(self, xy, seeds=None):
         """Fresh sampling states (an array of PIXEL_DTYPE) for the pixels `xy` (reshapes to (n, 2)
         uint32: x, y): the stream std::minstd_rand(seed), sum and samples 0.  seeds=None: the
@@ -417,6 +460,17 @@ class Scene:
                        "plane_tests": int(ctr[CTR_PLANES]), "errors": int(ctr[CTR_ERRORS]), "aux_visits": int(ctr[CTR_AUX]),
                        "fallbacks": int(ctr[CTR_FALLBACKS]), "fallbacks_ray": int(ctr[CTR_FALLBACKS_RAY]),
                        "samples": added}
+
+    def selftest_features(self, xy):
+        """Scene.features' records computed on the host (camera_ray, the query state machine, the
+        shade lookup): returns (records, counters), the counters named as pt_stats names them"""
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        out = np.zeros(len(xy), FEATURE_DTYPE)
+        ctr = np.zeros(8, np.uint64)
+        _check(_lib.pt_selftest_features_host(self._h, len(xy), _ptr(xy), _ptr(out), _ptr(ctr)))
+        return out, {"rays": int(ctr[CTR_RAYS]), "node_visits": int(ctr[CTR_NODES]), "prim_tests": int(ctr[CTR_PTESTS]),
+                     "plane_tests": int(ctr[CTR_PLANES]), "errors": int(ctr[CTR_ERRORS]), "aux_visits": int(ctr[CTR_AUX]),
+                     "fallbacks": int(ctr[CTR_FALLBACKS]), "fallbacks_ray": int(ctr[CTR_FALLBACKS_RAY])}
 
     def selftest_render_host(self, x0, y0, w, h, spp=0, traversal=TRAVERSAL_REPLAY):
         rad = np.zeros((h, w, 3), np.float32)
@@ -615,6 +669,21 @@ class Session:
         _check(_lib.pt_session_refine(self._h, C.byref(o), C.byref(res)))
         return res.as_dict()
 
+    def features(self, dev=None, stats=False):
+        """Every owned pixel's first-hit feature record, for the pixel's centre (x + 0.5, y + 0.5), in
+        export_states' order (rank_pixels' order): an array of FEATURE_DTYPE, or with `dev` -- a 16-byte
+        aligned device address or an object with data_ptr(), room for n_pixels records of 64 bytes -- a
+        fill of it (returns dev).  Nothing of the session changes.  stats=True: returns (records, the
+        call's stats dict)."""
+        n = self.n_pixels
+        st = Stats()
+        if dev is not None:
+            _check(_lib.pt_session_features(self._h, _addr(dev), n, C.byref(st)))
+            return (dev, st.as_dict()) if stats else dev
+        out = np.zeros(n, FEATURE_DTYPE)
+        _check(_lib.pt_session_features_host(self._h, _ptr(out), n, C.byref(st)))
+        return (out, st.as_dict()) if stats else out
+
     def close(self):
         if getattr(self, "_h", None) and _lib is not None:
             _lib.pt_session_free(self._h)
@@ -656,6 +725,45 @@ class RayQuery:
     def close(self):
         if getattr(self, "_h", None) and _lib is not None:
             _lib.pt_rayq_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class FeatureQuery:
+    """First-hit features for positions already on the device (include/pt.h first-hit features):
+    one context per scene and device, for runs of up to max_points positions."""
+
+    def __init__(self, scene, max_points=FEATS_CHUNK, device=0):
+        self.scene = scene
+        self.max_points = max_points
+        self._h = _P()
+        _check(_lib.pt_featq_create(scene._h, device, max_points, C.byref(self._h)))
+
+    def run(self, d_xy, d_out, n=None, stream=None):
+        """Enqueue n positions on `stream` (a hipStream_t address; None = the null stream).  d_xy /
+        d_out: device addresses, or objects with data_ptr() -- torch tensors of 2 float32 per
+        position and 64 bytes per record (FEATURE_DTYPE), used in place; n defaults to the
+        position tensor's element count / 2."""
+        if n is None:
+            n = d_xy.numel() // 2
+        _check(_lib.pt_featq_run(self._h, stream, n, _addr(d_xy), _addr(d_out)))
+
+    def stats(self):
+        """Wait for the last run; the counters and kernel time of the runs since the last call."""
+        st = Stats()
+        _check(_lib.pt_featq_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.pt_featq_free(self._h)
             self._h = None
 
     __del__ = close

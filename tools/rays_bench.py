@@ -11,7 +11,7 @@ stream; `--warmup` runs, then `--runs` timed ones.  Several forms alternate run 
 one process, and their hit buffers must be equal byte for byte: each `--form NAME[,LIB[,TUNE]]`
 is a libpt.so (empty: the tree's build; the kernel's plain form is built with
 `make OUT=build_plain DEFS=-DPT_RAYS_PLAIN`) and the PT_TUNE string its context is made under
-(`rays_service=N`).  The spread is that of one form's repeated runs: (max - min) / median.
+(`rays_service=N`); a ptrace.py beside LIB is loaded for it (another commit's build).  The spread is that of one form's repeated runs: (max - min) / median.
 
 Algorithmic bytes per ray come from the counters times the record sizes (aux node 128 B,
 reference node 32 B, primitive 48 B, plane record 80 B) plus the 24-B ray and the 24-B hit.
@@ -34,12 +34,17 @@ import _util as U  # noqa: E402
 
 
 def load_ptrace(lib, tag):
-    """ptrace over `lib` (None: the tree's build) as its own module"""
+    """ptrace over `lib` (None: the tree's build) as its own module; a ptrace.py beside `lib` -- the
+    build of another commit, whose library may lack this tree's newer entry points -- is the one loaded"""
     old = os.environ.get("PT_LIB")
+    src = os.path.join(U.PKG, "ptrace.py")
     if lib:
         os.environ["PT_LIB"] = os.path.abspath(lib)
+        beside = os.path.join(os.path.dirname(os.path.abspath(lib)), "ptrace.py")
+        if os.path.exists(beside):
+            src = beside
     try:
-        spec = importlib.util.spec_from_file_location("ptrace_" + tag, os.path.join(U.PKG, "ptrace.py"))
+        spec = importlib.util.spec_from_file_location("ptrace_" + tag, src)
         mod = importlib.util.module_from_spec(spec)
         spec.loader.exec_module(mod)
     finally:
