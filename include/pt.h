@@ -550,6 +550,74 @@ int pt_scene_shade(const pt_scene* s, pt_prim_shade* out, size_t n);
 /* Host only: the scene's BG_COLOR */
 int pt_scene_background(const pt_scene* s, float rgb[3]);
 
+/* ------------------------------------------------------------ guided filter
+ * A feature-guided a-trous denoise of a frame (additions to ABI 6: no existing struct or function
+ * changed).  No reference counterpart.  Everything is f32, every operation rounded, no FMA, in the
+ * order written here: a float32 restatement agrees bit for bit (tests/_filter.py is one).
+ *
+ * A frame is a window w x h of the image, row-major, top row first: radiance (3 x f32 per pixel,
+ * pt_render's layout), one pt_feature per pixel for the pixel's centre
+ * (float(x0 + x) + 0.5f, float(y0 + y) + 0.5f), and the options below.
+ *
+ * The guide of a pixel (32 B): n[3], t, a[3] = albedo, cls.  cls = 0 on a miss (id < 0), otherwise
+ * 1 + material + 4 * (emission[0] != 0 || emission[1] != 0 || emission[2] != 0).  n, t and a are the
+ * record's words (the library's records hold zeros there on a miss).
+ *
+ * Constants: ga = sigma_a * sigma_a; ia = ga > 0 ? 1.f / ga : 0.f.  Per level L = 0 .. levels - 1:
+ * s = 1 << L, sc = sigma_c * 2^-L, gc = sc * sc, ic = gc > 0 ? 1.f / gc : 0.f.  Per pixel p:
+ * gz = sigma_z * t_p; gz = gz * gz; iz = gz > 0 ? 1.f / gz : 0.f.  (Selects: a NaN takes 0.)
+ *
+ * One level (level 0 reads the input, level L the output of level L - 1).  A colour is finite when
+ * its three channels are.  A pixel whose own colour is not finite keeps its three words.  Otherwise,
+ * with K = {1/16, 1/4, 3/8, 1/4, 1/16}, acc = (0, 0, 0) and ws = 0, the 25 taps dy = -2 .. 2 (outer),
+ * dx = -2 .. 2 (inner), q = (x + dx * s, y + dy * s):
+ *   the centre tap has w = 9/64;
+ *   a tap outside the window, one with cls_q != cls_p and one whose colour is not finite are skipped;
+ *   otherwise  d = (n_p.x * n_q.x + n_p.y * n_q.y) + n_p.z * n_q.z;  d = d > 0 ? d : 0;  normal_pow2
+ *              times d = d * d;  wn = cls_p == 0 ? 1 : d;
+ *              dz = t_p - t_q;  ez = dz * dz;
+ *              ea = (da0 * da0 + da1 * da1) + da2 * da2  over a_p - a_q;  ec the same over the current
+ *              level's c_p - c_q;
+ *              D = ((1 + ez * iz) * (1 + ea * ia)) * (1 + ec * ic);
+ *              w = (K[dy + 2] * K[dx + 2] * wn) / D;  w = w > 0 ? w : 0;
+ *   a tap that is not skipped adds acc_c = acc_c + w * c_q,c and ws = ws + w.
+ * Then inv = 1.f / ws (ws >= 9/64) and out_c = acc_c * inv.  The last level's output is the result;
+ * its optional 8-bit form is the render's tonemap, gamma and rounding of it (pt_pixel_resolve's). */
+enum { PT_FILTER_ROWMAJOR = 0,       /* the input is w * h pixels, row-major */
+       PT_FILTER_TILES = 1 };        /* the input is a world-1 session's packed dev_radiance of the same
+                                      * window: exactly what pt_unpack_tiles_f32(w, h, 0, 1, ..) reads */
+typedef struct pt_filter_opts {
+    uint32_t levels;                 /* 1 .. 8 */
+    float    sigma_c, sigma_z, sigma_a;   /* each >= 0 and finite; 0 switches that weight off */
+    uint32_t normal_pow2;            /* 0 .. 8 */
+    uint32_t layout;                 /* PT_FILTER_*: of the input; the output is row-major either way */
+} pt_filter_opts;
+/* levels 3, sigma_c 1, sigma_z 0.05, sigma_a 0.1, normal_pow2 5, row-major */
+void pt_filter_opts_default(pt_filter_opts* o);
+typedef struct pt_filtq pt_filtq;
+/* a filter context on `device` for the window (x0, y0, w, h) of the scene's image; w = 0: the full
+ * image; a window outside the image, or one of more than 2^27 pixels: PT_E_INVALID.  Prepares the
+ * scene if needed; the scene must outlive the context.  Computes the window's guides here, once,
+ * with a feature query on the pixel centres.  The context holds 64 B of device memory per pixel. */
+int pt_filtq_create(pt_scene* s, int device, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, pt_filtq** out);
+/* replaces the guides by ones packed from the caller's w * h records (device, 16-byte aligned,
+ * row-major); asynchronous on `stream`, after the context's previous run */
+int pt_filtq_set_features(pt_filtq* q, void* stream, const pt_feature* dev_features);
+/* asynchronous on `stream` (a hipStream_t; NULL = the null stream), one launch per level.  dev_in
+ * (opts->layout), dev_out (w * h * 3 f32) and the optional dev_rgb (w * h * 3 u8; may be NULL) are
+ * device pointers on the context's device, dev_in and dev_out 4-byte aligned.  Ranges that overlap,
+ * NULL pointers and invalid options: PT_E_INVALID, nothing enqueued, nothing written.  One run at a
+ * time per context: a run first waits (on the host) for the context's previous run. */
+int pt_filtq_run(pt_filtq* q, void* stream, const pt_filter_opts* opts, const float* dev_in, float* dev_out,
+                 uint8_t* dev_rgb);
+/* waits for the last run; fills kernel_ms (the runs since the last call) and rays (the guide points
+ * traced since the last call); every other field 0 */
+int pt_filtq_stats(pt_filtq* q, pt_stats* st);
+void pt_filtq_free(pt_filtq* q);
+/* convenience, host pointers, synchronous: a context, an upload, a run, a download.  rgb may be NULL */
+int pt_filter(pt_scene* s, int device, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, const pt_filter_opts* opts,
+              const float* in, float* out, uint8_t* rgb);
+
 const char* pt_last_error(void);
 int pt_abi_version(void);
 
@@ -576,6 +644,11 @@ int pt_selftest_pixels_host(pt_scene* s, uint64_t n, pt_pixel_state* state, cons
  * run to completion, then the shade lookup, by the inline functions k_feats runs.  counters8 as
  * pt_selftest_paths_host fills it (rays = n); may be NULL.  Needs no GPU. */
 int pt_selftest_features_host(pt_scene* s, uint64_t n, const float* xy, pt_feature* out, uint64_t* counters8);
+/* pt_filtq_run's result on the host for a w x h frame: the guides packed from `features` (w * h
+ * records, row-major), then the levels, by the inline functions k_filter_guides and k_filter run, on
+ * one thread.  in: opts->layout; out: w * h * 3 f32.  Needs no device and no scene. */
+int pt_selftest_filter_host(uint32_t w, uint32_t h, const pt_feature* features, const pt_filter_opts* opts,
+                            const float* in, float* out);
 /* the 256-entry gamma threshold table used by the device tonemap */
 int pt_selftest_gamma_table(const pt_scene* s, float* thr256);
 /* session set-up without a device: the geometry (o's rank, world, window, traversal; o->device is

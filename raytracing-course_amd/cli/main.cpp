@@ -6,6 +6,8 @@
 //     PT_SPP_LAUNCH=<k> samples per kernel launch (default auto)
 //     PT_GATHER=rccl|host  framebuffer gather (default: RCCL when PT_NGPU > 1)
 //     PT_QUIET=1      no progress bar
+//     PT_FILTER=<levels>  write the image from the guided filter of the radiance (1..8 levels, the
+//                     other options at their defaults; unset or 0: the render's own image)
 //     PT_STATS=1      print rays / Mray/s / timings to stderr (2: also the phase times)
 //     PT_FULL_EXIT=1  tear the scene and the HIP runtime down before exiting (default: the
 //                     process leaves right after the PPM is closed; rocprofv3 needs the full exit)
@@ -72,10 +74,24 @@ int main(int argc, char** argv) {
     }
     std::vector<uint8_t> rgb((size_t)info.width * info.height * 3);
     pt_stats st;
-    if (pt_render(s, &o, rgb.data(), nullptr, &st) != PT_OK) {
+    // PT_FILTER=<levels>: the render's radiance through the guided filter, the image from its 8-bit form
+    const int filter_levels = env_int("PT_FILTER", 0);
+    std::vector<float> rad(filter_levels ? rgb.size() : 0);
+    if (pt_render(s, &o, rgb.data(), filter_levels ? rad.data() : nullptr, &st) != PT_OK) {
         fprintf(stderr, "pt_render: %s\n", pt_last_error());
         pt_scene_free(s);
         return 1;
+    }
+    if (filter_levels) {
+        pt_filter_opts fo;
+        pt_filter_opts_default(&fo);
+        fo.levels = (uint32_t)filter_levels;   // (outside 1..8: the library's refusal)
+        std::vector<float> out(rad.size());
+        if (pt_filter(s, dev0, 0, 0, 0, 0, &fo, rad.data(), out.data(), rgb.data()) != PT_OK) {
+            fprintf(stderr, "pt_render: %s\n", pt_last_error());
+            pt_scene_free(s);
+            return 1;
+        }
     }
     t_render = ms();
     if (pt_write_ppm(argv[2], info.width, info.height, rgb.data()) != PT_OK) {

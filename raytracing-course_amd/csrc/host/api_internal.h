@@ -13,6 +13,9 @@
 //   featq.cpp     the first-hit feature engine: the closest hit and the hit primitive's scene data for the
 //                 caller's image-plane positions, and for a session's pixel centres (pt_featq_*, pt_features,
 //                 pt_session_features)
+//   filtq.cpp     the guided filter of a frame: guides from the first-hit features of the pixel centres, one
+//                 kernel launch per a-trous level (pt_filtq_*, pt_filter), and the same on the host
+//                 (pt_selftest_filter_host)
 //   pathq.cpp     the batch radiance engine: RayTrace for the caller's rays (pt_pathq_*, pt_radiance,
 //                 pt_camera_rays)
 //   pixq.cpp      the pixel-sample engine: Sample's loop for the caller's pixel states (pt_pixq_*,
@@ -47,6 +50,7 @@
 
 #include "../device/pt_coop.h"
 #include "../device/pt_feats.h"
+#include "../device/pt_filter.h"
 #include "../device/pt_kernels.h"
 #include "../device/pt_paths.h"
 #include "../device/pt_pixels.h"
@@ -402,6 +406,20 @@ struct pt_featq {
     bool pending = false;           // ... whose time has not been added to kernel_ms yet
     double kernel_ms = 0.0;         // since the last pt_featq_stats
     unsigned long long seen[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the counters at the last pt_featq_stats
+};
+
+// A filter context (filtq.cpp): a window's guides and the two colour buffers the levels alternate between.
+struct pt_filtq {
+    pt_scene* sc = nullptr;
+    int dev = 0;
+    uint32_t x0 = 0, y0 = 0, w = 0, h = 0;
+    // one allocation: the guides (32 B per pixel) | two sets of 16-B colours
+    unsigned char* arena = nullptr;
+    const float* thr = nullptr;     // the scene's gamma thresholds on the device
+    hipEvent_t e0 = nullptr, e1 = nullptr;   // around the last run's kernels
+    bool pending = false;           // ... whose time has not been added to kernel_ms yet
+    double kernel_ms = 0.0;         // since the last pt_filtq_stats
+    uint64_t guide_points = 0;      // traced for the guides since the last pt_filtq_stats
 };
 
 // A batch radiance context (pathq.cpp): the scene's copy on one device and the run state of k_paths.

@@ -49,6 +49,7 @@ FEATURE_DTYPE = np.dtype([("id", np.int32), ("t", np.float32), ("n", np.float32,
                           ("material", np.uint32), ("type", np.uint32), ("reserved", np.uint32)])
 SHADE_DTYPE = np.dtype([("albedo", np.float32, (3,)), ("ior", np.float32), ("emission", np.float32, (3,)),
                         ("material", np.uint32)])
+FILTER_ROWMAJOR, FILTER_TILES = 0, 1   # pt_filter_opts.layout (include/pt.h "guided filter")
 FEATS_CHUNK = 1 << 22    # pt_features moves the points in chunks of at most this many
 PIXELS_CHUNK = 1 << 22   # pt_sample_pixels moves the records in chunks of at most this many
 # pt_selftest_math's ops (include/pt.h PT_MATH_*): name -> (op, record in, record out; None = 3n f32)
@@ -131,6 +132,25 @@ class RefineResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class FilterOpts(C.Structure):
+    """pt_filter_opts; FilterOpts.default(**changes) starts from pt_filter_opts_default"""
+    _fields_ = [("levels", C.c_uint32), ("sigma_c", C.c_float), ("sigma_z", C.c_float), ("sigma_a", C.c_float),
+                ("normal_pow2", C.c_uint32), ("layout", C.c_uint32)]
+
+    @classmethod
+    def default(cls, **changes):
+        o = cls()
+        _lib.pt_filter_opts_default(C.byref(o))
+        for k, v in changes.items():
+            if k not in dict(cls._fields_):
+                raise TypeError("no filter option %r" % k)
+            setattr(o, k, v)
+        return o
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _P = C.c_void_p
 _sig = {
     "pt_scene_load": (C.c_int, [C.c_char_p, C.POINTER(_P)]),
@@ -200,6 +220,14 @@ _sig = {
     "pt_session_features_host": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(Stats)]),
     "pt_scene_shade": (C.c_int, [_P, _P, C.c_size_t]),
     "pt_scene_background": (C.c_int, [_P, _P]),
+    "pt_filter_opts_default": (None, [C.POINTER(FilterOpts)]),
+    "pt_filtq_create": (C.c_int, [_P, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    "pt_filtq_set_features": (C.c_int, [_P, _P, _P]),
+    "pt_filtq_run": (C.c_int, [_P, _P, C.POINTER(FilterOpts), _P, _P, _P]),
+    "pt_filtq_stats": (C.c_int, [_P, C.POINTER(Stats)]),
+    "pt_filtq_free": (None, [_P]),
+    "pt_filter": (C.c_int, [_P, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(FilterOpts), _P, _P,
+                            _P]),
     "pt_last_error": (C.c_char_p, []),
     "pt_abi_version": (C.c_int, []),
     "pt_selftest_ray_intersection": (C.c_int, [_P, C.c_int32, C.c_uint32, _P, _P, _P, _P]),
@@ -208,6 +236,7 @@ _sig = {
     "pt_selftest_paths_host": (C.c_int, [_P, C.c_uint64, _P, _P, _P]),
     "pt_selftest_pixels_host": (C.c_int, [_P, C.c_uint64, _P, _P, C.c_uint32, _P]),
     "pt_selftest_features_host": (C.c_int, [_P, C.c_uint64, _P, _P, _P]),
+    "pt_selftest_filter_host": (C.c_int, [C.c_uint32, C.c_uint32, _P, C.POINTER(FilterOpts), _P, _P]),
     "pt_selftest_gamma_table": (C.c_int, [_P, _P]),
     "pt_selftest_wave_plan": (C.c_int, [_P, C.POINTER(SessionOpts), C.c_uint32, C.c_char_p, C.c_size_t]),
     "pt_selftest_state_slots": (C.c_int, [_P, C.POINTER(SessionOpts), C.c_uint64, _P, _P]),
@@ -368,6 +397,25 @@ class Scene:
         st = Stats()
         _check(_lib.pt_features(self._h, device, len(xy), _ptr(xy), _ptr(out), C.byref(st)))
         return out, st.as_dict()
+
+    def filter(self, radiance, window=None, device=0, rgb=False, **opts):
+        """The guided filter of a frame on the GPU (include/pt.h "guided filter"): `radiance` is the
+        window's (h, w, 3) float32 -- window = (x0, y0, w, h), None: the full image -- or, with
+        layout=FILTER_TILES, a world-1 session's packed radiance of it.  opts: FilterOpts' fields over
+        pt_filter_opts_default.  Returns the filtered (h, w, 3) float32; with rgb=True also its 8-bit form."""
+        o = FilterOpts.default(**opts)
+        x0, y0, w, h = window or (0, 0, 0, 0)
+        if not w:
+            i = self.info
+            w, h = i["width"], i["height"]
+        radiance = np.ascontiguousarray(radiance, np.float32)
+        need = (((w + 15) // 16) * ((h + 15) // 16) * 256 if o.layout == FILTER_TILES else w * h) * 3
+        if radiance.size != need:
+            raise ValueError("the frame holds %d floats, the window and layout need %d" % (radiance.size, need))
+        out = np.zeros((h, w, 3), np.float32)
+        img = np.zeros((h, w, 3), np.uint8) if rgb else None
+        _check(_lib.pt_filter(self._h, device, x0, y0, w, h, C.byref(o), _ptr(radiance), _ptr(out), _ptr(img)))
+        return (out, img) if rgb else out
 
     def shade(self):
         """Every primitive's albedo, ior, emission and material (an array of SHADE_DTYPE) in the
@@ -773,6 +821,73 @@ class FeatureQuery:
 
     def __exit__(self, *a):
         self.close()
+
+
+class FilterQuery:
+    """The guided filter for frames already on the device (include/pt.h "guided filter"): one context
+    per scene, device and window (None: the full image); it holds the window's guides."""
+
+    def __init__(self, scene, window=None, device=0):
+        self.scene = scene
+        x0, y0, w, h = window or (0, 0, 0, 0)
+        if not w:
+            i = scene.info
+            w, h = i["width"], i["height"]
+        self.window = (x0, y0, w, h)
+        self._h = _P()
+        _check(_lib.pt_filtq_create(scene._h, device, x0, y0, w, h, C.byref(self._h)))
+
+    def set_features(self, d_features, stream=None):
+        """Replace the guides by ones packed from the caller's w * h FEATURE_DTYPE records on the
+        device (16-byte aligned, row-major)."""
+        _check(_lib.pt_filtq_set_features(self._h, stream, _addr(d_features)))
+
+    def run(self, d_in, d_out, d_rgb=None, stream=None, **opts):
+        """Enqueue one filter run on `stream` (a hipStream_t address; None = the null stream).  d_in /
+        d_out / d_rgb: device addresses, or objects with data_ptr() -- the input in opts' layout, the
+        (h, w, 3) float32 output and the optional (h, w, 3) uint8 one.  opts: FilterOpts' fields over
+        pt_filter_opts_default, or opts=<a FilterOpts>."""
+        o = opts.pop("opts", None)
+        if o is None:
+            o = FilterOpts.default(**opts)
+        elif opts:
+            raise TypeError("either opts= or single options")
+        _check(_lib.pt_filtq_run(self._h, stream, C.byref(o), _addr(d_in), _addr(d_out),
+                                 _addr(d_rgb) if d_rgb is not None else None))
+
+    def stats(self):
+        """Wait for the last run; kernel_ms of the runs and rays = the guide points traced since the
+        last call."""
+        st = Stats()
+        _check(_lib.pt_filtq_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.pt_filtq_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def selftest_filter_host(features, radiance, w, h, **opts):
+    """FilterQuery.run's result computed on the host, for a w x h frame with the caller's FEATURE_DTYPE
+    records (row-major): the filtered (h, w, 3) float32.  Needs no device and no scene."""
+    o = opts.pop("opts", None) or FilterOpts.default(**opts)
+    features = np.ascontiguousarray(features, FEATURE_DTYPE).reshape(-1)
+    radiance = np.ascontiguousarray(radiance, np.float32)
+    need = (((w + 15) // 16) * ((h + 15) // 16) * 256 if o.layout == FILTER_TILES else w * h) * 3
+    if len(features) != w * h or radiance.size != need:
+        raise ValueError("w * h records and the layout's floats are needed")
+    out = np.zeros((h, w, 3), np.float32)
+    _check(_lib.pt_selftest_filter_host(w, h, _ptr(features), C.byref(o), _ptr(radiance), _ptr(out)))
+    return out
 
 
 class PathQuery:
