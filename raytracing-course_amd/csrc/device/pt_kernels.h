@@ -346,6 +346,11 @@ static_assert((1u << CTR_RAYS | 1u << CTR_NODES | 1u << CTR_PTESTS | 1u << CTR_P
                1u << CTR_COOP_NODES | 1u << CTR_COOP_PTESTS | 1u << CTR_SHORT | 1u << CTR_HANDON |
                1u << CTR_COOP_AUX) == (1u << 14) - 1u && 14u <= CTR_HO,
               "statistics counter slots: two names share a slot, or one reaches the hand-off sites");
+// a diagnostic slot beside them (no pt_stats field: PT_TUNE roundlog=2 prints it per round): the
+// path engine's finished queries that found their done ring full and were still waiting in their
+// lanes when their round ended (counted where they are suspended, off the trip)
+enum : uint32_t { CTR_DQ_FULL = 14u };
+static_assert(CTR_DQ_FULL >= 14u && CTR_DQ_FULL < CTR_HO, "the diagnostic slot lies between the named slots and the hand-off sites");
 // the hand-off sites (include/pt.h PT_HO_*, which the host checks these against)
 enum : uint32_t { HO_SUSPEND = 0u, HO_FLUSH, HO_RINGOUT, HO_EXACT, HO_SIDE_TAKE, HO_SIDE_YIELD, HO_SIDE_HANDON,
                   HO_GROW_YIELD, HO_GROW_HANDON, HO_N };

@@ -226,9 +226,13 @@ __device__ __forceinline__ void path_suspend(PathLds<NQ>& L, const LdsMemN<64u *
         K.st.rec[2u * slot] = lds_get(L.H, (uint32_t)q.cid);   // the chain leaves the workgroup
     }
     const uint32_t ns = (uint32_t)__popcll(__ballot(active));
+    // (of them, the finished queries that found their done ring full and still waited for room;
+    // counted here, off the trip: a test or a round log can tell that the full-ring path ran)
+    const uint32_t nw = (uint32_t)__popcll(__ballot(active && q.phase == Q_DONE));
     if (lane_id() == 0u && ns) {
         atomicSub(&L.resident, ns);
         atomicAdd(ctr_copy(K0.counters) + CTR_HO + HO_SUSPEND, (unsigned long long)ns);
+        if (nw) atomicAdd(ctr_copy(K0.counters) + CTR_DQ_FULL, (unsigned long long)nw);
     }
     pf.exit_budget();
 }
@@ -369,7 +373,7 @@ __device__ __forceinline__ void path_aux_extra(const WaveParams& P, bool active,
         const bool a2 = active && q.phase == Q_AUX && !(q.node & PT_LEAFQ);
         if (__ballot(a2) == 0ull) break;
         pf.extra_aux((uint32_t)__popcll(__ballot(a2)));
-        if (a2) q_aux_step(P.S, q, C, stk);
+        if (a2) q_aux_step<false>(P.S, q, C, stk);   // (its decide: the trip's one, path_query_wave)
     }
 }
 // Finished queries -> this wave's done ring wq, in lane order, as far as it has room
@@ -528,8 +532,14 @@ __device__ __forceinline__ void path_query_wave(const WaveParams& P, PathLds<NQ>
             if (want_probe && !probe_go) kind = 7u;
             pf.kinds(kind == 0u, pick != 0u, kind == 0u || kind == pick);
             pf.kind_mix(kind == 0u ? ((q.node & PT_LEAFQ) ? 1u : 0u) : kind == pick ? kind + 1u : 7u);
-            if (kind == 0u || kind == pick) q_step(P.S, q, N.C, stk);
+            // the trip's steps leave a lane that reached a decision in Q_DECIDE; one q_decide
+            // resolves them all (its code is issued for the whole wave whenever a lane has
+            // one: once per trip, not once per step).  A lane at a decision takes no extra
+            // aux step (path_aux_extra asks for Q_AUX), and one whose decide starts another
+            // aux pass takes that pass's first step in the next trip.
+            if (kind == 0u || kind == pick) q_step<false>(P.S, q, N.C, stk);
             path_aux_extra(P, active, q, N.C, stk, pf);
+            if (active && q.phase == Q_DECIDE) q_decide(q);
         }
         pf.step_end();
         path_retire(L, wq, active, slot, q, dq_res, N.fallbacks, pf);

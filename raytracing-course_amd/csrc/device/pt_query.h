@@ -155,7 +155,7 @@ struct Query {
     f3 inv;                     // 1/d (IEEE, once per ray)
     float P;                    // closest plane t (the BVH bound at the root)
     // small state packed into two registers
-    uint32_t phase : 3;         // Q_* (Q_DECIDE only inside q_exec)
+    uint32_t phase : 3;         // Q_* (Q_DECIDE only inside q_exec, or up to the caller's q_decide: q_exec<false>)
     uint32_t walk : 2;          // Q_REPLAY step kind: R_CAND, R_WALK_E, R_WALK_N
     uint32_t par : 1;           // near-zero direction component: exact node tests, robust aux boxes
     uint32_t robust : 1;        // leaf check: the ray crosses the leaf box robustly (t1c, mc valid)
@@ -823,8 +823,11 @@ PT_HD void q_exec_kind(const SceneView& S, Query& q, QCounts& C, Mem& stk, const
 }
 
 // one step's compute: the step kind's transition, its edit of the hit list (each kind of
-// edit only when a lane of the wave has one), then the precomputed accepts
-template <class Mem>
+// edit only when a lane of the wave has one), then the precomputed accepts.
+// DECIDE = false leaves a lane that reached a decision in phase Q_DECIDE: the caller runs
+// q_decide itself before anything else looks at the phase (the path engine's query wave:
+// one q_decide per trip, after the trip's steps).
+template <bool DECIDE = true, class Mem>
 PT_HD void q_exec(const SceneView& S, Query& q, QCounts& C, Mem& stk, const F4 r[8] QP_ARG) {
     QEdit ed{QE_NONE, 0u, 0.f, 0, 0.f};
 #ifdef PT_QPROF_DEV
@@ -838,7 +841,9 @@ PT_HD void q_exec(const SceneView& S, Query& q, QCounts& C, Mem& stk, const F4 r
     if (pt_any(ed.op == QE_REJECT)) {
         if (ed.op == QE_REJECT) q_drop_rejected(q);
     }
-    if (q.phase == Q_DECIDE) q_decide(q);
+    if constexpr (DECIDE) {
+        if (q.phase == Q_DECIDE) q_decide(q);
+    }
 }
 
 PT_HD F4 blob_piece(const SceneView& S, uint32_t off) {
@@ -850,7 +855,7 @@ PT_HD F4 blob_piece(const SceneView& S, uint32_t off) {
 // Every lane loads 8 pieces (q_addr repeats a step's last piece): loading only
 // the distinct ones measured -5 % (the exec-mask branches cost more than the
 // repeated loads, which hit the same line).
-template <class Mem>
+template <bool DECIDE = true, class Mem>
 PT_HD void q_step(const SceneView& S, Query& q, QCounts& C, Mem& stk) {
     uint32_t off[8];
     q_addr(S, q, off);
@@ -859,22 +864,24 @@ PT_HD void q_step(const SceneView& S, Query& q, QCounts& C, Mem& stk) {
     for (int k = 0; k < 8; ++k) r[k] = blob_piece(S, off[k]);
 #ifdef PT_QPROF_DEV
     uint32_t qp[5];
-    q_exec(S, q, C, stk, r, qp);
+    q_exec<DECIDE>(S, q, C, stk, r, qp);
 #else
-    q_exec(S, q, C, stk, r);
+    q_exec<DECIDE>(S, q, C, stk, r);
 #endif
 }
 
 // One aux-node step only (a lane whose next step is an aux node: phase Q_AUX, node
 // not a leaf); the decisions a pass end leaves are resolved as in q_exec.
-template <class Mem>
+template <bool DECIDE = true, class Mem>
 PT_HD void q_aux_step(const SceneView& S, Query& q, QCounts& C, Mem& stk) {
     const uint32_t b = S.o_aux + q.node * (uint32_t)(PT_AUXW * sizeof(AuxSL));
     F4 r[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) r[k] = blob_piece(S, b + 16u * (uint32_t)k);
     q_exec_aux(S, q, C, stk, r);
-    if (q.phase == Q_DECIDE) q_decide(q);
+    if constexpr (DECIDE) {
+        if (q.phase == Q_DECIDE) q_decide(q);
+    }
 }
 
 // exact stack DFS for the rays the replay leaves (planes again + bvh_exact:
@@ -892,16 +899,32 @@ PT_HD int q_exact(const SceneView& S, const Ray& ray, Stack& stk, Hit& out, QCou
     return id;
 }
 
-// whole query on one thread (host tests / reference form of the state machine)
-template <class Stack>
-PT_HD int q_run(const SceneView& S, const Ray& ray, Stack& stk, Hit& out, QCounts& C, uint32_t& exact_used) {
+// One trip of a path-engine query lane (pt_path.hip path_query_wave) on one thread: a step
+// and up to `aux_extra` more aux-node steps, none of them deciding, then the trip's one
+// q_decide.  A lane at a decision after the first step takes no extra step, and a decide
+// that starts another aux pass leaves that pass's first step to the next trip.
+template <class Mem>
+PT_HD void q_trip(const SceneView& S, Query& q, QCounts& C, Mem& stk, uint32_t aux_extra) {
+    q_step<false>(S, q, C, stk);
+    for (uint32_t x = 0; x < aux_extra && q.phase == Q_AUX && !(q.node & PT_LEAFQ); ++x) q_aux_step<false>(S, q, C, stk);
+    if (q.phase == Q_DECIDE) q_decide(q);
+}
+
+// whole query on one thread (host tests / reference form of the state machine);
+// TRIP: in the path engine's trips (q_trip) instead of single steps
+template <bool TRIP, class Stack>
+PT_HD int q_run_as(const SceneView& S, const Ray& ray, Stack& stk, Hit& out, QCounts& C, uint32_t& exact_used,
+                   uint32_t aux_extra) {
     Query q;
     float P;
     int pid;
     q_planes(S, ray, P, pid);
     C.planes += S.n_planes;
     q_init(S, ray, P, pid, q);
-    while (q.phase == Q_AUX || q.phase == Q_REPLAY) q_step(S, q, C, stk);
+    while (q.phase == Q_AUX || q.phase == Q_REPLAY) {
+        if constexpr (TRIP) q_trip(S, q, C, stk, aux_extra);
+        else q_step(S, q, C, stk);
+    }
     exact_used = q.phase == Q_EXACT ? 1u : 0u;
     if (exact_used) return q_exact(S, ray, stk, out, C);
     if (q.res_id >= 0) {
@@ -910,6 +933,15 @@ PT_HD int q_run(const SceneView& S, const Ray& ray, Stack& stk, Hit& out, QCount
         if (!ok || f2u(out.t) != f2u(q.res_t)) C.planes |= 0x80000000u;   // must never happen (tests check)
     }
     return q.res_id;
+}
+template <class Stack>
+PT_HD int q_run(const SceneView& S, const Ray& ray, Stack& stk, Hit& out, QCounts& C, uint32_t& exact_used) {
+    return q_run_as<false>(S, ray, stk, out, C, exact_used, 0u);
+}
+template <class Stack>
+PT_HD int q_run_trip(const SceneView& S, const Ray& ray, Stack& stk, Hit& out, QCounts& C, uint32_t& exact_used,
+                     uint32_t aux_extra) {
+    return q_run_as<true>(S, ray, stk, out, C, exact_used, aux_extra);
 }
 
 }  // namespace pt

@@ -124,6 +124,9 @@ const Rccl& rccl() {
 //   qengine=coop      host self-tests: the cooperative engine's query algorithm (pt_coop.h)
 //   qengine=mega      host self-tests, traversal 0: the megakernel's query with the filtered node
 //                     tests (ray_intersection<true>, the code of engine=mega's k_trace)
+//   qengine=trip      host self-tests, traversal 0 (pt_selftest_ray_intersection): the state machine in
+//                     the path engine's trips (q_run_trip: a step and aux_extra more aux-node steps,
+//                     then one q_decide)
 //   prepstats=1       pt_scene_prepare's per-stage times on stderr
 std::string tune_str(const char* key) {
     // the single-variable switches of earlier builds are ignored now: say so once

@@ -189,9 +189,11 @@ int report_round(pt_session* ss, int level, uint32_t target, uint32_t chains, bo
     if (chains) {
         const double ms = now - ss->roundlog_t;
         const PathShape sh = path_shape(ss->plan, chains, sparse, side);
-        fprintf(stderr, "round %u chains %u -> %u+%u (%s%s, nq %u x %u) %.2f ms rays %llu %.0f Mray/s", ss->rounds, chains,
-                ss->ctl_host[pt::C_FRESH], ss->ctl_host[pt::C_CARRY], chains < ss->plan.lowq ? "low" : "full",
-                side ? "+side" : "", sh.nq, sh.grid, ms, rays - ss->roundlog_rays, (rays - ss->roundlog_rays) / ms / 1e3);
+        // (dq_full: the session's finished queries so far suspended while their done ring was full)
+        fprintf(stderr, "round %u chains %u -> %u+%u (%s%s, nq %u x %u) %.2f ms rays %llu %.0f Mray/s dq_full %llu", ss->rounds,
+                chains, ss->ctl_host[pt::C_FRESH], ss->ctl_host[pt::C_CARRY], chains < ss->plan.lowq ? "low" : "full",
+                side ? "+side" : "", sh.nq, sh.grid, ms, rays - ss->roundlog_rays, (rays - ss->roundlog_rays) / ms / 1e3,
+                c[pt::CTR_DQ_FULL]);
         if (level == 3) {
             std::vector<uint4> rec(2ull * ss->n_slots);
             HIP_TRY(hipMemcpy(rec.data(), ss->st.rec, rec.size() * sizeof(uint4), hipMemcpyDeviceToHost));

@@ -44,6 +44,9 @@ int pt_selftest_ray_intersection(pt_scene* s, int32_t traversal, uint32_t n, con
     pt::Counts C{};
     const bool coop = tune_str("qengine") == "coop";   // the cooperative engine's query (pt_coop.h)
     const bool mega = tune_str("qengine") == "mega";   // the megakernel's FAST query (k_trace<true>)
+    // the state machine in the path engine's trips (q_trip), PT_TUNE aux_extra extra aux-node steps each
+    const bool trip = tune_str("qengine") == "trip";
+    const uint32_t aux_extra = (uint32_t)std::max(0, tune_int("aux_extra", 1));
     for (uint32_t i = 0; i < n; ++i) {
         pt::Ray r;
         r.o = pt::mk3(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]);
@@ -55,7 +58,9 @@ int pt_selftest_ray_intersection(pt_scene* s, int32_t traversal, uint32_t n, con
         } else if (traversal == PT_TRAVERSAL_REPLAY) {
             pt::QCounts Q{0u, 0u, 0u, 0u};
             uint32_t ex = 0;
-            id = coop ? pt::qc_query(V, r, stk, h, Q, ex) : pt::q_run(V, r, stk, h, Q, ex);
+            id = coop   ? pt::qc_query(V, r, stk, h, Q, ex)
+                 : trip ? pt::q_run_trip(V, r, stk, h, Q, ex, aux_extra)
+                        : pt::q_run(V, r, stk, h, Q, ex);
             if (Q.planes & 0x80000000u) return fail(PT_E_INVALID, "recomputed closest hit differs from the query's");
             C.rays++;
             C.nodes += Q.nodes; C.ptests += Q.ptests; C.planes += Q.planes; C.aux += Q.aux; C.fallbacks += ex;
