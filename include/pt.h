@@ -658,6 +658,13 @@ int pt_selftest_gamma_table(const pt_scene* s, float* thr256);
  * aux_stack_words (the scene's wide aux traversal stack, which a carry record holds).
  * Prepares the scene if needed. */
 int pt_selftest_wave_plan(pt_scene* s, const pt_session_opts* o, uint32_t cus, char* buf, size_t cap);
+/* a batch context's launch shape without a device: the workgroup and the resident grid of a context
+ * with fold records (pt_pathq, pt_pixq) on a device of `cus` compute units that hold `per_cu`
+ * workgroups of `block` threads each, at RAY_DEPTH `depth` -- per_cu * cus workgroups unless their
+ * lanes' fold records (16 B x depth each) exceed 1 GiB, then fewer, then narrower ones; PT_E_OOM
+ * where one wave per compute unit still exceeds it. */
+int pt_selftest_fold_shape(uint32_t cus, uint32_t per_cu, uint32_t block, uint32_t depth, uint32_t* block_out,
+                           uint32_t* grid_out);
 /* per record the session slot it would land in, by the functions k_states_mark uses compiled
  * for the host: >= 0 slot, -1 in the image but not this session's, -2 outside the image or a
  * bad rng word (of a pixel that is this session's: another's record is -1 whatever it holds).

@@ -57,13 +57,7 @@ __global__ void __launch_bounds__(256) k_feats_positions(FeatPosParams P) {
 
 hipError_t pt_launch_feats(const pt::FeatsParams& p, uint32_t grid, uint32_t block, hipStream_t s, hipEvent_t e0,
                            hipEvent_t e1) {
-    hipError_t e = hipMemsetAsync(p.head, 0, PT_RAYS_CTL_BYTES, s);
-    if (e != hipSuccess) return e;
-    if (e0 && (e = hipEventRecord(e0, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(pt::k_feats, dim3(grid), dim3(block), (block / 64u) * 64u * 4u * (p.aux_words + 1u), s, p);
-    hipLaunchKernelGGL(pt::k_feats_exact, dim3(256), dim3(64), 64u * 4u * (p.dfs_words + 1u), s, p);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    return e1 ? hipEventRecord(e1, s) : hipSuccess;
+    return pt::launch_rays_pair(pt::k_feats, pt::k_feats_exact, p, grid, block, s, e0, e1);
 }
 
 hipError_t pt_launch_feats_positions(const pt::FeatPosParams& p, hipStream_t s) {

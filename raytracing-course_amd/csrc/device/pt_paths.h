@@ -36,8 +36,9 @@ struct PathsParams {
 
 }  // namespace pt
 
-// workgroups of `block` threads and `lds_bytes` of LDS that one compute unit holds of k_paths
-hipError_t pt_paths_occupancy(uint32_t block, size_t lds_bytes, int* per_cu);
+// workgroups of `block` threads, each lane with its LDS column (pt_batch.h lane_lds_bytes), that one
+// compute unit holds of k_paths
+hipError_t pt_paths_occupancy(uint32_t block, uint32_t aux_words, uint32_t dfs_words, int* per_cu);
 // k_paths on `s`, after the control block's memset; `block` = threads per workgroup (a multiple of 64
 // whose stacks fit the workgroup's LDS), `grid` at most the workgroups the fold area was sized for;
 // e0 / e1 around the kernel

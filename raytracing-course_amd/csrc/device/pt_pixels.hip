@@ -13,26 +13,17 @@
 // step by the exact stack DFS, on the lane's own LDS words.
 #include <hip/hip_runtime.h>
 
+#include "pt_batch.h"
 #include "pt_pixels.h"
 #include "pt_wave.h"
 
 namespace pt {
 
-// the statistics a wave gathered, flushed once (one atomic per counter and wave)
-struct PixelStats {
-    QCounts C{0u, 0u, 0u, 0u};
-    uint32_t rays = 0u, err = 0u, exact = 0u, exact_ray = 0u, samples = 0u;
+// the wave's statistics, and the samples its records finished
+struct PixelStats : QStats {
+    uint32_t samples = 0u;
     __device__ __forceinline__ void flush(unsigned long long* counters) const {
-        unsigned long long* ctr = ctr_copy(counters);
-        wave_add_u64(ctr + CTR_RAYS, rays);
-        wave_add_u64(ctr + CTR_NODES, C.nodes);
-        wave_add_u64(ctr + CTR_PTESTS, C.ptests);
-        wave_add_u64(ctr + CTR_PLANES, C.planes);
-        wave_add_u64(ctr + CTR_ERRORS, err);
-        wave_add_u64(ctr + CTR_AUX, C.aux);
-        wave_add_u64(ctr + CTR_FALLBACKS, exact);
-        wave_add_u64(ctr + CTR_FALLBACKS_RAY, exact_ray);
-        wave_add_u64(ctr + PT_PIXELS_CTR_SAMPLES, samples);
+        wave_add_u64(QStats::flush(counters) + PT_PIXELS_CTR_SAMPLES, samples);
     }
 };
 
@@ -48,22 +39,6 @@ struct PixelLane {
     uint32_t left;    // samples still to finish, the running one included
     uint32_t nv;      // the running sample's vertices so far (fold records written)
 };
-
-// the lane's LDS column: the query's aux stack, or (the aux stack is dead by then) the exact DFS's
-struct PixelStack {
-    uint32_t* base;
-    uint32_t aux_words, dfs_words;
-    __device__ __forceinline__ LdsMemN<64u> aux() const { return LdsMemN<64u>{base, aux_words, aux_words}; }
-    __device__ __forceinline__ LdsMemN<64u> dfs() const { return LdsMemN<64u>{base, dfs_words, dfs_words}; }
-};
-__device__ __forceinline__ PixelStack pixel_stack(const PixelsParams& P, uint32_t* lds) {
-    const uint32_t words = (P.aux_words > P.dfs_words ? P.aux_words : P.dfs_words) + 1u;
-    // [word][lane] per wave
-    return PixelStack{lds + (threadIdx.x >> 6) * 64u * words + (threadIdx.x & 63u), P.aux_words, P.dfs_words};
-}
-__device__ __forceinline__ HbmVStore pixel_fold(const PixelsParams& P) {
-    return HbmVStore{P.fold + ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * P.depth};
-}
 
 // a record's two 16-B pieces
 __device__ __forceinline__ uint4* rec_piece(const PixelsParams& P, uint32_t i, uint32_t k) {
@@ -86,62 +61,7 @@ __device__ __forceinline__ void depth0_samples(const PixelsParams& P, Rng& R, ui
     }
 }
 
-// RayIntersection's start for `ray`: the planes, then the BVH query's set-up
-__device__ __forceinline__ void start_query(const PixelsParams& P, const Ray& ray, Query& q, PixelStats& st) {
-    float pt;
-    int pid;
-    q_planes(P.S, ray, pt, pid);
-    st.C.planes += P.S.n_planes;
-    q_init(P.S, ray, pt, pid, q);
-    st.rays++;
-    if (q.phase == Q_EXACT) st.exact_ray++;   // a non-finite ray: the exact DFS by design
-}
-
-// The vertex of a query that left Q_AUX / Q_REPLAY (trace_path_with's loop body after the query).
-// The hit is recomputed from its primitive as q_run does (the probe computes t only); a Q_EXACT
-// query is answered here by the exact DFS.  True: the path goes on with `ray`; false: it has
-// ended with `leaf` below its nv fold records.
-__device__ __forceinline__ bool sample_vertex(const PixelsParams& P, const Query& q, Rng& R, uint32_t& nv,
-                                              const PixelStack& ls, HbmVStore& vs, PixelStats& st, Ray& ray, f3& leaf) {
-    ray = q.ray;
-    Hit h;
-    int id;
-    if (q.phase == Q_EXACT) {
-        LdsMemN<64u> xs = ls.dfs();
-        id = q_exact(P.S, ray, xs, h, st.C);
-        st.exact++;
-    } else {
-        id = q.res_id;
-        if (id >= 0) {
-            const bool ok = prim_intersect(P.S.prims[id], ray, h);
-            if (!ok || f2u(h.t) != f2u(q.res_t)) st.err++;   // must never happen (the tests check)
-        }
-    }
-    if (id < 0) {
-        leaf = P.S.bg;
-        return false;
-    }
-    uint32_t idm;
-    float s1, s2;
-    const bool cont = shade_vertex(P.S, R, ray, h, id, idm, s1, s2);
-    vs.put(nv++, idm, s1, s2);   // nv < depth: a record follows a query, and a path has at most depth queries
-    leaf = mk3(0.f, 0.f, 0.f);
-    return cont && nv != P.depth;   // RayTrace(.., 0) = 0
-}
-
-// an ended path's value: the backward fold, deepest vertex first (trace_path_with's order)
-__device__ __forceinline__ f3 fold_sample(const PixelsParams& P, uint32_t nv, const HbmVStore& vs, f3 leaf) {
-    f3 Lr = leaf;
-    for (uint32_t k = nv; k > 0u;) {
-        --k;
-        uint32_t idm;
-        float s1, s2;
-        vs.get(k, idm, s1, s2);
-        Lr = fold_vertex(P.S, Lr, idm, s1, s2);
-    }
-    return Lr;
-}
-// ... into its record: summary = summary + RayTrace(..) (src/scene.cpp:199), and the sample counted.
+// An ended path's value (fold_path) into its record: summary = summary + RayTrace(..) (src/scene.cpp:199), and the sample counted.
 // One 16-B load and one 16-B store of the record's second piece, which no other lane touches.
 __device__ __forceinline__ void add_sample(const PixelsParams& P, uint32_t i, f3 Lr) {
     uint4* p = rec_piece(P, i, 1u);
@@ -149,8 +69,6 @@ __device__ __forceinline__ void add_sample(const PixelsParams& P, uint32_t i, f3
     const f3 sum = mk3(u2f(b.x), u2f(b.y), u2f(b.z)) + Lr;
     *p = make_uint4(f2u(sum.x), f2u(sum.y), f2u(sum.z), b.w + 1u);
 }
-
-__device__ __forceinline__ bool q_running(const Query& q) { return q.phase == Q_AUX || q.phase == Q_REPLAY; }
 
 // The occupancy the compiler is held to, in waves per SIMD (`make DEFS=-DPT_PIXELS_WAVES_PER_EU=N`
 // builds another; 0 leaves the choice to the compiler: the table in DESIGN.md §4.7)
@@ -166,19 +84,14 @@ __device__ __forceinline__ bool q_running(const Query& q) { return q.phase == Q_
 #ifndef PT_PIXELS_PLAIN
 __global__ void __launch_bounds__(256) PT_PIXELS_OCC k_pixels(PixelsParams P) {
     extern __shared__ uint32_t lds_stack[];
-    const uint32_t lane = threadIdx.x & 63u;
-    const PixelStack ls = pixel_stack(P, lds_stack);
+    const LaneStack ls = lane_stack(P, lds_stack);
     LdsMemN<64u> stk = ls.aux();
-    HbmVStore vs = pixel_fold(P);
+    HbmVStore vs = lane_fold(P);
     PixelStats st;
     PixelLane L;
     L.q.phase = Q_DONE;
     bool have = false;        // this lane holds a record with samples left
-    // the wave's reservation [rnext, rnext + rleft) of record indices, and whether the work counter
-    // may still be below n (all three wave-uniform)
-    unsigned long long rnext = 0ull;
-    uint32_t rleft = 0u;
-    bool more = true;
+    WaveTake T{0u, true, 0ull};   // the wave's reservation of record indices (wave-uniform)
     // Why this loop ends, from the wave's own state alone (it waits for no other wave or workgroup
     // anywhere: the only shared word is the work counter, which is only ever added to; a record,
     // the fold records and the LDS column are one lane's own):
@@ -202,7 +115,7 @@ __global__ void __launch_bounds__(256) PT_PIXELS_OCC k_pixels(PixelsParams P) {
     //   * so the trips are bounded by the pulls, plus the steps of the queries of the samples of
     //     the records the wave took.
     for (;;) {
-        const bool run = have && q_running(L.q);
+        const bool run = have && q_running(L.q.phase);
         const unsigned long long mrun = __ballot(run);
         // The service step, once `service` lanes wait (a finished query, or empty) or none runs.
         // Not on every trip: a vertex recomputes its hit, samples and writes a fold record, a
@@ -213,9 +126,9 @@ __global__ void __launch_bounds__(256) PT_PIXELS_OCC k_pixels(PixelsParams P) {
             bool first = false;   // ... a sample's first: `ray` is the camera ray still to be drawn
             if (have && !run) {
                 f3 leaf;
-                start = sample_vertex(P, L.q, L.R, L.nv, ls, vs, st, ray, leaf);
+                start = lane_vertex(P.S, P.depth, L.q, L.R, L.nv, ls, vs, st, ray, leaf);
                 if (!start) {
-                    add_sample(P, L.idx, fold_sample(P, L.nv, vs, leaf));
+                    add_sample(P, L.idx, fold_path(P.S, L.nv, vs, leaf));
                     st.samples++;
                     if (--L.left != 0u) {
                         start = first = true;
@@ -225,24 +138,13 @@ __global__ void __launch_bounds__(256) PT_PIXELS_OCC k_pixels(PixelsParams P) {
                     }
                 }
             }
-            if (rleft == 0u && more) {
-                // one atomic per pull, by one lane, for the whole wave
-                unsigned long long got = 0ull;
-                if (lane == 0u) got = atomicAdd(P.head, (unsigned long long)P.batch);
-                // (lane 0's value in scalar registers: the reservation is wave-uniform)
-                const unsigned long long base =
-                    (unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(got >> 32)) << 32 |
-                    __builtin_amdgcn_readfirstlane((uint32_t)got);
-                rnext = base;
-                rleft = base < P.n ? (uint32_t)(P.n - base < P.batch ? P.n - base : P.batch) : 0u;
-                more = base + P.batch < P.n;
-            }
-            if (rleft != 0u) {
+            if (T.dry()) T.pull(P);
+            if (T.rleft != 0u) {
                 const unsigned long long m = __ballot(!have);
                 const uint32_t k = lanes_below(m);
-                if (!have && k < rleft) {
+                if (!have && T.holds(k)) {
                     // the next record: its first piece and its count (count 0: not a byte of it changes)
-                    const uint32_t i = (uint32_t)(rnext + k);
+                    const uint32_t i = (uint32_t)T.item(k);
                     const uint32_t count = rec_count(P, i);
                     if (count != 0u) {
                         const uint4 a = *rec_piece(P, i, 0u);
@@ -264,9 +166,7 @@ __global__ void __launch_bounds__(256) PT_PIXELS_OCC k_pixels(PixelsParams P) {
                         }
                     }
                 }
-                const uint32_t took = (uint32_t)__popcll(m) < rleft ? (uint32_t)__popcll(m) : rleft;
-                rnext += took;
-                rleft -= took;
+                T.advance(m);
             }
             // (one copy of the jitter and camera ray for the records' first and later samples, and
             // one of the planes and the set-up for the child rays and the camera rays)
@@ -276,10 +176,10 @@ __global__ void __launch_bounds__(256) PT_PIXELS_OCC k_pixels(PixelsParams P) {
                 ray = camera_sample(K.cam, L.R, L.x, L.y);
                 L.nv = 0u;
             }
-            if (start) start_query(P, ray, L.q, st);
-            if (rleft == 0u && !more && __ballot(have) == 0ull) break;
+            if (start) start_query(P.S, ray, L.q, st);
+            if (T.spent() && __ballot(have) == 0ull) break;
         }
-        if (have && q_running(L.q)) q_step(P.S, L.q, st.C, stk);
+        if (have && q_running(L.q.phase)) q_step(P.S, L.q, st.C, stk);
     }
     st.flush(P.counters);
 }
@@ -289,9 +189,9 @@ __global__ void __launch_bounds__(256) PT_PIXELS_OCC k_pixels(PixelsParams P) {
 // wave as slow as its longest record
 __global__ void __launch_bounds__(256) PT_PIXELS_OCC k_pixels(PixelsParams P) {
     extern __shared__ uint32_t lds_stack[];
-    const PixelStack ls = pixel_stack(P, lds_stack);
+    const LaneStack ls = lane_stack(P, lds_stack);
     LdsMemN<64u> stk = ls.aux();
-    HbmVStore vs = pixel_fold(P);
+    HbmVStore vs = lane_fold(P);
     PixelStats st;
     Query q;
     const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
@@ -307,11 +207,11 @@ __global__ void __launch_bounds__(256) PT_PIXELS_OCC k_pixels(PixelsParams P) {
             Ray ray = camera_sample(P.cam, R, a.z, a.w);
             uint32_t nv = 0u;
             for (;;) {
-                start_query(P, ray, q, st);
-                while (q_running(q)) q_step(P.S, q, st.C, stk);
+                start_query(P.S, ray, q, st);
+                while (q_running(q.phase)) q_step(P.S, q, st.C, stk);
                 f3 leaf;
-                if (sample_vertex(P, q, R, nv, ls, vs, st, ray, leaf)) continue;
-                sum = sum + fold_sample(P, nv, vs, leaf);
+                if (lane_vertex(P.S, P.depth, q, R, nv, ls, vs, st, ray, leaf)) continue;
+                sum = sum + fold_path(P.S, nv, vs, leaf);
                 break;
             }
         }
@@ -325,17 +225,11 @@ __global__ void __launch_bounds__(256) PT_PIXELS_OCC k_pixels(PixelsParams P) {
 
 }  // namespace pt
 
-hipError_t pt_pixels_occupancy(uint32_t block, size_t lds_bytes, int* per_cu) {
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, pt::k_pixels, (int)block, lds_bytes);
+hipError_t pt_pixels_occupancy(uint32_t block, uint32_t aux_words, uint32_t dfs_words, int* per_cu) {
+    return pt::lanes_occupancy(pt::k_pixels, block, aux_words, dfs_words, per_cu);
 }
 
 hipError_t pt_launch_pixels(const pt::PixelsParams& p, uint32_t grid, uint32_t block, hipStream_t s, hipEvent_t e0,
                             hipEvent_t e1) {
-    hipError_t e = hipMemsetAsync(p.head, 0, PT_PIXELS_CTL_BYTES, s);
-    if (e != hipSuccess) return e;
-    if (e0 && (e = hipEventRecord(e0, s)) != hipSuccess) return e;
-    const uint32_t words = (p.aux_words > p.dfs_words ? p.aux_words : p.dfs_words) + 1u;
-    hipLaunchKernelGGL(pt::k_pixels, dim3(grid), dim3(block), (block / 64u) * 64u * 4u * words, s, p);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    return e1 ? hipEventRecord(e1, s) : hipSuccess;
+    return pt::launch_lanes(pt::k_pixels, p, PT_PIXELS_CTL_BYTES, grid, block, s, e0, e1);
 }

@@ -4,7 +4,7 @@
 //
 // The engine itself -- the persistent refill loop, its service step, the exact list and the
 // per-wave counter flush -- is a template over a job type (rays_engine / rays_exact_engine below,
-// device compiles only), so that an engine with another source of rays and another record per item
+// device compiles only; the reservation, the statistics and the query's start are pt_batch.h's), so that an engine with another source of rays and another record per item
 // instantiates it and does not copy it: pt_rays.hip with the caller's rays and 24-B hits,
 // pt_feats.hip with the camera's rays and 64-B first-hit features.
 #pragma once
@@ -53,38 +53,14 @@ hipError_t pt_launch_rays(const pt::RaysParams& p, uint32_t grid, uint32_t block
 //   Ray  ray(size_t i) const                             the ray of item i
 //   void store(size_t i, int id, const Hit& h) const     item i's record from its closest hit (id < 0: a miss,
 //                                                        h then holds nothing)
-#include "pt_devutil.h"
+#include "pt_batch.h"
 
 namespace pt {
 
-// the statistics a wave gathered, flushed once (one atomic per counter and wave)
-struct RayStats {
-    QCounts C{0u, 0u, 0u, 0u};
-    uint32_t rays = 0u, err = 0u, exact = 0u, exact_ray = 0u;
-    __device__ __forceinline__ void flush(unsigned long long* counters) const {
-        unsigned long long* ctr = ctr_copy(counters);
-        wave_add_u64(ctr + CTR_RAYS, rays);
-        wave_add_u64(ctr + CTR_NODES, C.nodes);
-        wave_add_u64(ctr + CTR_PTESTS, C.ptests);
-        wave_add_u64(ctr + CTR_PLANES, C.planes);
-        wave_add_u64(ctr + CTR_ERRORS, err);
-        wave_add_u64(ctr + CTR_AUX, C.aux);
-        wave_add_u64(ctr + CTR_FALLBACKS, exact);
-        wave_add_u64(ctr + CTR_FALLBACKS_RAY, exact_ray);
-    }
-};
-
-// a lane takes item i: the planes, then the BVH query's set-up
+// a lane takes item i: RayIntersection's start for its ray
 template <class PARAMS, class JOB>
-__device__ __forceinline__ void take_ray(const PARAMS& P, const JOB& job, size_t i, Query& q, RayStats& st) {
-    const Ray ray = job.ray(i);
-    float pt;
-    int pid;
-    q_planes(P.S, ray, pt, pid);
-    st.C.planes += P.S.n_planes;
-    q_init(P.S, ray, pt, pid, q);
-    st.rays++;
-    if (q.phase == Q_EXACT) st.exact_ray++;   // a non-finite ray: the exact DFS by design
+__device__ __forceinline__ void take_ray(const PARAMS& P, const JOB& job, size_t i, Query& q, QStats& st) {
+    start_query(P.S, job.ray(i), q, st);
 }
 
 // A query that left Q_AUX / Q_REPLAY retires (every lane of the wave calls this; `fin` = this lane
@@ -92,7 +68,7 @@ __device__ __forceinline__ void take_ray(const PARAMS& P, const JOB& job, size_t
 // recomputed from its primitive exactly as q_run does (the probe computes t only).
 template <class PARAMS, class JOB>
 __device__ __forceinline__ void retire(const PARAMS& P, const JOB& job, bool fin, size_t i, const Query& q,
-                                       RayStats& st) {
+                                       QStats& st) {
     const bool ex = fin && q.phase == Q_EXACT;
     const uint32_t k = wave_append(P.exact_n, ex);
     if (ex) {
@@ -117,16 +93,12 @@ __device__ __forceinline__ void rays_engine(const PARAMS& P, const JOB& job) {
     const uint32_t lane = threadIdx.x & 63u;
     // [word][lane] per wave: words 0 .. aux_words - 1, then the trash word
     LdsMemN<64u> stk{lds_stack + (threadIdx.x >> 6) * 64u * (P.aux_words + 1u) + lane, P.aux_words, P.aux_words};
-    RayStats st;
+    QStats st;
     Query q;
     q.phase = Q_DONE;
     bool have = false;        // this lane holds a ray that has not retired
     size_t idx = 0;
-    // the wave's reservation [rnext, rnext + rleft) of item indices, and whether the work counter may
-    // still be below n (all three wave-uniform)
-    unsigned long long rnext = 0ull;
-    uint32_t rleft = 0u;
-    bool more = true;
+    WaveTake T{0u, true, 0ull};   // the wave's reservation of item indices (wave-uniform)
     // Why this loop ends, from the wave's own state alone (it waits for no other wave or workgroup
     // anywhere: the only shared words are the work counter and the exact list's count, both only
     // ever added to):
@@ -139,7 +111,7 @@ __device__ __forceinline__ void rays_engine(const PARAMS& P, const JOB& job) {
     //     finds nothing left and leaves;
     //   * so the trips are bounded by the pulls, plus the steps of the rays the wave took.
     for (;;) {
-        const bool run = have && (q.phase == Q_AUX || q.phase == Q_REPLAY);
+        const bool run = have && q_running(q.phase);
         const unsigned long long mrun = __ballot(run);
         // The service step, once `service` lanes wait (finished or empty) or none runs: the finished
         // lanes retire and the empty ones take items.  Not on every trip: a retiring lane recomputes
@@ -149,33 +121,20 @@ __device__ __forceinline__ void rays_engine(const PARAMS& P, const JOB& job) {
             const bool fin = have && !run;
             retire(P, job, fin, idx, q, st);
             if (fin) have = false;
-            if (rleft == 0u && more) {
-                // one atomic per pull, by one lane, for the whole wave
-                unsigned long long got = 0ull;
-                if (lane == 0u) got = atomicAdd(P.head, (unsigned long long)P.batch);
-                // (lane 0's value in scalar registers: the reservation is wave-uniform)
-                const unsigned long long base =
-                    (unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(got >> 32)) << 32 |
-                    __builtin_amdgcn_readfirstlane((uint32_t)got);
-                rnext = base;
-                rleft = base < P.n ? (uint32_t)(P.n - base < P.batch ? P.n - base : P.batch) : 0u;
-                more = base + P.batch < P.n;
-            }
-            if (rleft != 0u) {
+            if (T.dry()) T.pull(P);
+            if (T.rleft != 0u) {
                 const unsigned long long m = __ballot(!have);
                 const uint32_t k = lanes_below(m);
-                if (!have && k < rleft) {
-                    idx = (size_t)(rnext + k);
+                if (!have && T.holds(k)) {
+                    idx = (size_t)T.item(k);
                     take_ray(P, job, idx, q, st);
                     have = true;
                 }
-                const uint32_t took = (uint32_t)__popcll(m) < rleft ? (uint32_t)__popcll(m) : rleft;
-                rnext += took;
-                rleft -= took;
+                T.advance(m);
             }
-            if (rleft == 0u && !more && __ballot(have) == 0ull) break;
+            if (T.spent() && __ballot(have) == 0ull) break;
         }
-        if (have && (q.phase == Q_AUX || q.phase == Q_REPLAY)) q_step(P.S, q, st.C, stk);
+        if (have && q_running(q.phase)) q_step(P.S, q, st.C, stk);
     }
     st.flush(P.counters);
 }
@@ -187,7 +146,7 @@ __device__ __forceinline__ void rays_exact_engine(const PARAMS& P, const JOB& jo
     extern __shared__ uint32_t lds_stack[];
     const uint32_t n = *P.exact_n;
     LdsMemN<64u> stk{lds_stack + threadIdx.x, P.dfs_words, P.dfs_words};
-    RayStats st;
+    QStats st;
     for (uint32_t k = blockIdx.x * 64u + threadIdx.x; k < n; k += gridDim.x * 64u) {
         const size_t i = P.exact[k];
         const Ray ray = job.ray(i);
@@ -197,6 +156,20 @@ __device__ __forceinline__ void rays_exact_engine(const PARAMS& P, const JOB& jo
     }
     st.C.planes = 0u;   // (the refill loop counted these rays' plane tests when it took them)
     st.flush(P.counters);
+}
+
+// The engine's two kernels on `s`, after the control block's memset: `engine` (rays_engine) on
+// `grid` workgroups of `block` threads, then `exact` (rays_exact_engine); e0 / e1 around the two
+template <class KERNEL, class PARAMS>
+hipError_t launch_rays_pair(KERNEL engine, KERNEL exact, const PARAMS& p, uint32_t grid, uint32_t block, hipStream_t s,
+                            hipEvent_t e0, hipEvent_t e1) {
+    hipError_t e = hipMemsetAsync(p.head, 0, PT_RAYS_CTL_BYTES, s);
+    if (e != hipSuccess) return e;
+    if (e0 && (e = hipEventRecord(e0, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(engine, dim3(grid), dim3(block), (block / 64u) * 64u * 4u * (p.aux_words + 1u), s, p);
+    hipLaunchKernelGGL(exact, dim3(256), dim3(64), 64u * 4u * (p.dfs_words + 1u), s, p);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    return e1 ? hipEventRecord(e1, s) : hipSuccess;
 }
 
 }  // namespace pt

@@ -53,7 +53,7 @@ __global__ void __launch_bounds__(256) k_rays(RaysParams P) {
     extern __shared__ uint32_t lds_stack[];
     const uint32_t lane = threadIdx.x & 63u;
     LdsMemN<64u> stk{lds_stack + (threadIdx.x >> 6) * 64u * (P.aux_words + 1u) + lane, P.aux_words, P.aux_words};
-    RayStats st;
+    QStats st;
     const RaysJob job{P};
     const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
     // (a wave-uniform trip count: retire()'s append needs the whole wave)
@@ -63,7 +63,7 @@ __global__ void __launch_bounds__(256) k_rays(RaysParams P) {
         Query q;
         q.phase = Q_DONE;
         if (have) take_ray(P, job, i, q, st);
-        while (q.phase == Q_AUX || q.phase == Q_REPLAY) q_step(P.S, q, st.C, stk);
+        while (q_running(q.phase)) q_step(P.S, q, st.C, stk);
         retire(P, job, have, i, q, st);
     }
     st.flush(P.counters);
@@ -79,11 +79,5 @@ __global__ void __launch_bounds__(64) k_rays_exact(RaysParams P) {
 
 hipError_t pt_launch_rays(const pt::RaysParams& p, uint32_t grid, uint32_t block, hipStream_t s, hipEvent_t e0,
                           hipEvent_t e1) {
-    hipError_t e = hipMemsetAsync(p.head, 0, PT_RAYS_CTL_BYTES, s);
-    if (e != hipSuccess) return e;
-    if (e0 && (e = hipEventRecord(e0, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(pt::k_rays, dim3(grid), dim3(block), (block / 64u) * 64u * 4u * (p.aux_words + 1u), s, p);
-    hipLaunchKernelGGL(pt::k_rays_exact, dim3(256), dim3(64), 64u * 4u * (p.dfs_words + 1u), s, p);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    return e1 ? hipEventRecord(e1, s) : hipSuccess;
+    return pt::launch_rays_pair(pt::k_rays, pt::k_rays_exact, p, grid, block, s, e0, e1);
 }

@@ -9,6 +9,8 @@
 //   wave_plan.cpp the wavefront pass's launch shapes and capacities (plan_wave: no device needed)
 //   rounds.cpp    the wavefront pass: path rounds, early / final cooperative launches
 //   render.cpp    Scene::Render equivalent: per-GPU threads, the RCCL / host gather, PPM
+//   qctx.cpp      what the batch contexts below share: set-up, launch shape, statistics, the event timer and
+//                 (here, as templates) their creation and the one-shot host forms' chunk loop
 //   rayq.cpp      the ray-query engine: closest-hit queries for the caller's rays (pt_rayq_*, pt_intersect)
 //   featq.cpp     the first-hit feature engine: the closest hit and the hit primitive's scene data for the
 //                 caller's image-plane positions, and for a session's pixel centres (pt_featq_*, pt_features,
@@ -28,13 +30,15 @@
 //                 noise / plan / refine), and the plan on the host (pt_selftest_refine_plan)
 //   selftest.cpp  host execution of the device query / integrator code, and pt_selftest_math (the
 //                 device code's scalar functions on the host or in k_selftest_math) (tests only; one
-//                 hook, pt_selftest_wave_plan, is in session.cpp beside the set-up it reports)
+//                 hook, pt_selftest_wave_plan, is in session.cpp beside the set-up it reports, another,
+//                 pt_selftest_fold_shape, in qctx.cpp)
 #pragma once
 #include "pt.h"
 
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <algorithm>
 #include <chrono>
@@ -377,36 +381,44 @@ struct pt_session {
     pt::FeatXY* feat_xy = nullptr;
 };
 
-// A ray-query context (rayq.cpp): the scene's copy on one device and the run state of k_rays.
-struct pt_rayq {
-    pt_scene* sc = nullptr;
-    int dev = 0;
-    uint64_t max_rays = 0;
-    pt::RaysParams p{};             // the view of the device copy and the arena's pieces (rays, hits, n, batch: per run)
-    // one allocation: the control block | the statistics counters | the exact list (max_rays words)
-    unsigned char* arena = nullptr;
-    uint32_t block = 256, max_grid = 1;   // k_rays' workgroup (its lanes' stacks fit the LDS) and the resident grid
+namespace pti {
+
+// The events around a context's last run and the time they add up to (qctx.cpp).
+struct RunTimer {
     hipEvent_t e0 = nullptr, e1 = nullptr;   // around the last run's kernels
     bool pending = false;           // ... whose time has not been added to kernel_ms yet
-    double kernel_ms = 0.0;         // since the last pt_rayq_stats
-    unsigned long long seen[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the counters at the last pt_rayq_stats
+    double kernel_ms = 0.0;         // since the context's last *_stats
+    bool create();                  // the two events (false: hipEventCreate failed)
+    // the time of the last run's kernels, once they have finished (also: what the run used is free)
+    int settle();
+    void destroy();                 // waits for a pending run, which still uses the context's arena
 };
 
-// A first-hit feature context (featq.cpp): the scene's copy on one device and the run state of k_feats.
-struct pt_featq {
+// What every batch context is (qctx.cpp): the scene's copy on one device, one arena -- the run's
+// control block | the statistics counters | the engine's own tail --, the launch shape and the run
+// state.  An engine's context is this and its parameter block `p`: the view of the device copy and
+// the arena's pieces, the per-run members filled by its *_run.
+struct QueryCtx {
     pt_scene* sc = nullptr;
     int dev = 0;
-    uint64_t max_points = 0;
-    pt::FeatsParams p{};            // the view of the device copy, the camera and the arena's pieces (xy, out, n, batch:
-                                    // per run)
-    // one allocation: the control block | the statistics counters | the exact list (max_points words)
+    uint64_t max_items = 0;
     unsigned char* arena = nullptr;
-    uint32_t block = 256, max_grid = 1;   // k_feats' workgroup (its lanes' stacks fit the LDS) and the resident grid
-    hipEvent_t e0 = nullptr, e1 = nullptr;   // around the last run's kernels
-    bool pending = false;           // ... whose time has not been added to kernel_ms yet
-    double kernel_ms = 0.0;         // since the last pt_featq_stats
-    unsigned long long seen[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the counters at the last pt_featq_stats
+    unsigned long long* counters = nullptr;   // PT_CTR_COPIES x PT_CTR_STRIDE, in the arena behind the control block
+    uint32_t block = 256, max_grid = 1;   // the kernel's workgroup (its lanes' stacks fit the LDS) and the resident grid
+    RunTimer t;
+    unsigned long long seen[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // the counters at the last *_stats
 };
+
+}  // namespace pti
+
+// rayq.cpp, k_rays: the tail is the exact list (max_items words); p's rays, hits, n, batch: per run
+struct pt_rayq : pti::QueryCtx { pt::RaysParams p{}; };
+// featq.cpp, k_feats: p holds the camera besides; the tail as pt_rayq's; xy, out, n, batch: per run
+struct pt_featq : pti::QueryCtx { pt::FeatsParams p{}; };
+// pathq.cpp, k_paths: the tail is the resident lanes' fold records, which max_grid is sized with; in, out, n, batch: per run
+struct pt_pathq : pti::QueryCtx { pt::PathsParams p{}; };
+// pixq.cpp, k_pixels: p holds the camera besides; the tail as pt_pathq's; state, counts, spp, n, batch: per run
+struct pt_pixq : pti::QueryCtx { pt::PixelsParams p{}; };
 
 // A filter context (filtq.cpp): a window's guides and the two colour buffers the levels alternate between.
 struct pt_filtq {
@@ -416,43 +428,122 @@ struct pt_filtq {
     // one allocation: the guides (32 B per pixel) | two sets of 16-B colours
     unsigned char* arena = nullptr;
     const float* thr = nullptr;     // the scene's gamma thresholds on the device
-    hipEvent_t e0 = nullptr, e1 = nullptr;   // around the last run's kernels
-    bool pending = false;           // ... whose time has not been added to kernel_ms yet
-    double kernel_ms = 0.0;         // since the last pt_filtq_stats
+    pti::RunTimer t;
     uint64_t guide_points = 0;      // traced for the guides since the last pt_filtq_stats
 };
 
-// A batch radiance context (pathq.cpp): the scene's copy on one device and the run state of k_paths.
-struct pt_pathq {
-    pt_scene* sc = nullptr;
-    int dev = 0;
-    uint64_t max_paths = 0;
-    pt::PathsParams p{};            // the view of the device copy and the arena's pieces (in, out, n, batch: per run)
-    // one allocation: the control block | the statistics counters | the resident lanes' fold records
-    unsigned char* arena = nullptr;
-    uint32_t block = 256, max_grid = 1;   // k_paths' workgroup (its lanes' stacks fit the LDS) and the resident
-                                          // grid, which the fold area is sized for
-    hipEvent_t e0 = nullptr, e1 = nullptr;   // around the last run's kernel
-    bool pending = false;           // ... whose time has not been added to kernel_ms yet
-    double kernel_ms = 0.0;         // since the last pt_pathq_stats
-    unsigned long long seen[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the counters at the last pt_pathq_stats
-};
+namespace pti {
 
-// A pixel-sample context (pixq.cpp): the scene's copy on one device and the run state of k_pixels.
-struct pt_pixq {
-    pt_scene* sc = nullptr;
-    int dev = 0;
-    uint64_t max_pixels = 0;
-    pt::PixelsParams p{};           // the view of the device copy, the camera and the arena's pieces (state, counts,
-                                    // spp, n, batch: per run)
-    // one allocation: the control block | the statistics counters | the resident lanes' fold records
-    unsigned char* arena = nullptr;
-    uint32_t block = 256, max_grid = 1;   // k_pixels' workgroup (its lanes' stacks fit the LDS) and the resident
-                                          // grid, which the fold area is sized for
-    hipEvent_t e0 = nullptr, e1 = nullptr;   // around the last run's kernel
-    bool pending = false;           // ... whose time has not been added to kernel_ms yet
-    double kernel_ms = 0.0;         // since the last pt_pixq_stats
-    unsigned long long seen[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // the counters at the last pt_pixq_stats
+// ---- the batch contexts' core (qctx.cpp): each rule of set-up, shape, statistics and the one-shot
+// host forms stated once
+constexpr size_t kQCtrBytes = PT_CTR_COPIES * PT_CTR_STRIDE * sizeof(unsigned long long);
+// *_create's checks -- the scene, the range of `max_items` (the message names the caller's
+// parameter, `name`) and the device --, then the prepared scene's copy on the device (made current)
+// and its compute units
+int qctx_open(pt_scene* s, int device, uint64_t max_items, const char* name, DevScene** ds, uint32_t* cus);
+// A lane's stack words: the aux stack as deep as the wide aux tree can need (so no query outgrows
+// it: Query::sp counts it in 7 bits, pt_scene_prepare rejects deeper trees), and the exact DFS's
+struct LaneWords { uint32_t aux_words, dfs_words; };
+LaneWords lane_words(const pt_scene* s);
+// The widest workgroup, from *block down to 64 threads, whose lanes' LDS columns (pt_batch.h
+// lane_lds_bytes) fit a workgroup's LDS; false: not even 64 lanes' do (*block is 64 then)
+bool fit_block(uint32_t aux_words, uint32_t dfs_words, uint32_t* block);
+// The resident grid of an engine with fold records (RAY_DEPTH x 16 B per resident lane): per_cu
+// workgroups on each compute unit, unless the fold area then exceeds 1 GiB -- fewer workgroups then,
+// after that narrower ones, down to one wave per compute unit; PT_E_OOM where that is still too much
+struct GridShape { uint32_t block, max_grid; };
+int fold_shape(uint32_t cus, uint32_t per_cu, uint32_t block, uint32_t depth, GridShape* out);
+// ... for a context: the block fit (PT_E_SCENE), `occupancy` asked for `kernel` (what the compiler's
+// registers and the LDS let a compute unit hold: the waves are persistent, a workgroup beyond that
+// would start when another has left, and find no work), fold_shape; q's block and max_grid set, the
+// fold area's size in *fold_bytes
+int qctx_fold_shape(QueryCtx* q, LaneWords w, uint32_t cus, uint32_t depth,
+                    hipError_t (*occupancy)(uint32_t, uint32_t, uint32_t, int*), const char* kernel, size_t* fold_bytes);
+// The arena -- ctl_bytes | counters | tail_bytes --, control block and counters zeroed, and the
+// timer's events.  `what` names the engine in the messages; alloc_fail_code is the code of a failed hipMalloc
+int qctx_alloc(QueryCtx* q, size_t ctl_bytes, size_t tail_bytes, const char* what, int alloc_fail_code);
+// A run's shape: no more workgroups than the resident grid or than n needs; and the items a wave
+// reserves per pull of the work counter: an eighth of its share, from a full wave to 512
+// (same-address atomics serialise chip-wide: one per item-sized refill would set the rate)
+struct RunShape { uint32_t grid, batch; };
+RunShape qctx_shape(const QueryCtx* q, uint64_t n);
+// *_stats: the settled time and the counters' first n_counters slots, summed over the copies, since
+// the last call (c, if given: those n_counters differences), as pt_stats
+int qctx_stats(QueryCtx* q, uint32_t n_counters, pt_stats* st, unsigned long long* c = nullptr);
+void qctx_close(QueryCtx* q);   // the pending run waited for, events and arena freed (q itself stays)
+
+// *_create: the checks and the device copy, a new context, `fill` for the engine's own set-up
+// (int fill(Q*, const DevScene&, uint32_t cus)); the context freed again where that fails
+template <class Q, class Fill>
+int qctx_create(pt_scene* s, int device, uint64_t max_items, const char* name, Q** out, Fill fill) {
+    if (!s || !out) return fail(PT_E_INVALID, "null argument");
+    DevScene* ds = nullptr;
+    uint32_t cus = 0;
+    int rc = qctx_open(s, device, max_items, name, &ds, &cus);
+    if (rc) return rc;
+    Q* q = new Q();
+    q->sc = s;
+    q->dev = device;
+    q->max_items = max_items;
+    if ((rc = fill(q, *ds, cus))) {
+        qctx_close(q);
+        delete q;
+        return rc;
+    }
+    *out = q;
+    return PT_OK;
+}
+template <class Q>
+void qctx_free(Q* q) {
+    if (!q) return;
+    qctx_close(q);
+    delete q;
+}
+
+// host <-> device copies of the one-shot forms (`what` failed: PT_E_HIP)
+int copy_up(void* dev, const void* host, size_t bytes, const char* what);
+int copy_down(void* host, const void* dev, size_t bytes, const char* what);
+
+// A context kind's public calls, for run_chunks
+template <class Q>
+struct QueryApi {
+    int (*create)(pt_scene*, int, uint64_t, Q**);
+    int (*stats)(Q*, pt_stats*);
+    void (*free)(Q*);
 };
+// The one-shot host forms (pt_intersect, pt_radiance, pt_sample_pixels, pt_features): a context
+// for chunks of at most 2^22 items, two device buffers of item_bytes[k] per item (0: none, the
+// pointer stays null), then per chunk `up(d, at, m)`, `run(q, d, m)` on the null stream -- which
+// orders the copies around the run --, `down(d, at, m)`; the context's stats into `stats` if given.
+// buf_fail / buf_msg: a failed buffer hipMalloc's code and message.
+template <class Q, class Up, class Run, class Down>
+int run_chunks(pt_scene* s, int device, uint64_t n, pt_stats* stats, const QueryApi<Q>& api, size_t item_bytes0,
+               size_t item_bytes1, int buf_fail, const char* buf_msg, Up up, Run run, Down down) {
+    constexpr uint64_t kChunk = 1ull << 22;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (n == 0) return PT_OK;
+    const uint64_t cap = std::min(n, kChunk);
+    Q* q = nullptr;
+    int rc = api.create(s, device, cap, &q);
+    if (rc) return rc;
+    const size_t item_bytes[2] = {item_bytes0, item_bytes1};
+    void* d[2] = {nullptr, nullptr};
+    auto done = [&](int code) {
+        (void)hipFree(d[0]);
+        (void)hipFree(d[1]);
+        api.free(q);
+        return code;
+    };
+    for (int k = 0; k < 2; ++k)
+        if (item_bytes[k] && hipMalloc(&d[k], cap * item_bytes[k]) != hipSuccess) return done(fail(buf_fail, buf_msg));
+    for (uint64_t at = 0; at < n; at += cap) {
+        const uint64_t m = std::min(cap, n - at);
+        if ((rc = up(d, at, m)) || (rc = run(q, d, m)) || (rc = down(d, at, m))) return done(rc);
+    }
+    if (stats && (rc = api.stats(q, stats))) return done(rc);
+    return done(PT_OK);
+}
+
+}  // namespace pti
 
 #pragma GCC visibility pop

@@ -18,21 +18,6 @@ static_assert(offsetof(pt_feature, t) == offsetof(pt_ray_hit, t) && offsetof(pt_
 namespace pti {
 namespace {
 
-constexpr size_t kCtrBytes = PT_CTR_COPIES * PT_CTR_STRIDE * sizeof(unsigned long long);
-constexpr uint64_t kChunk = 1ull << 22;   // pt_features: points per upload / run / download
-constexpr uint32_t kMaxLds = 65536u;      // LDS a workgroup may ask for
-
-// the time of the last run's kernels, once they have finished (also: the control block is free)
-int settle(pt_featq* q) {
-    if (!q->pending) return PT_OK;
-    HIP_TRY(hipEventSynchronize(q->e1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, q->e0, q->e1));
-    q->kernel_ms += ms;
-    q->pending = false;
-    return PT_OK;
-}
-
 // the session's feature context and its pixels' centres, made at the first pt_session_features (a
 // session that never asks has the memory and the launches it always had)
 int ensure_features(pt_session* ss, uint64_t n) {
@@ -72,52 +57,28 @@ using namespace pti;
 extern "C" {
 
 int pt_featq_create(pt_scene* s, int device, uint64_t max_points, pt_featq** out) {
-    if (!s || !out) return fail(PT_E_INVALID, "null argument");
-    if (max_points == 0 || max_points >= (1ull << 32)) return fail(PT_E_INVALID, "max_points must be in [1, 2^32)");
-    int rc = check_device(device);
-    if (rc) return rc;
-    if ((rc = pt_scene_prepare(s))) return rc;
-    DevScene* ds = nullptr;
-    double up_ms = 0.0;
-    if ((rc = ensure_device_scene(s, device, false, &ds, &up_ms))) return rc;
-    DevProps props;
-    if ((rc = device_props(device, &props))) return rc;
-    auto* q = new pt_featq();
-    q->sc = s;
-    q->dev = device;
-    q->max_points = max_points;
-    auto cleanup = [&](int code) {
-        pt_featq_free(q);
-        return code;
-    };
-    // the lanes' aux stacks, the workgroup and the resident grid: k_rays' rules (rayq.cpp)
-    const uint32_t aux_words = std::min<uint32_t>(
-        PT_QUERY_SP_MAX, std::max({lane_words(s, PT_TRAVERSAL_REPLAY), s->auxw_stack, 1u}));
-    while (q->block > 64u && q->block * 4u * (aux_words + 1u) > kMaxLds) q->block /= 2u;
-    q->max_grid = (uint32_t)props.cus * (2048u / q->block);
-    const size_t bytes = PT_RAYS_CTL_BYTES + kCtrBytes + (size_t)max_points * 4u;
-    if (hipSetDevice(device) != hipSuccess) return cleanup(fail(PT_E_HIP, "hipSetDevice failed"));
-    if (hipMalloc(reinterpret_cast<void**>(&q->arena), bytes) != hipSuccess)
-        return cleanup(fail(PT_E_OOM, "feature buffers: hipMalloc failed"));
-    if (hipMemset(q->arena, 0, PT_RAYS_CTL_BYTES + kCtrBytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-        hipEventCreate(&q->e0) != hipSuccess || hipEventCreate(&q->e1) != hipSuccess)
-        return cleanup(fail(PT_E_HIP, "feature set-up failed"));
-    q->p.S = device_view(s, *ds);
-    q->p.cam = make_cam(s);
-    q->p.head = reinterpret_cast<unsigned long long*>(q->arena);
-    q->p.exact_n = reinterpret_cast<uint32_t*>(q->arena + 8);
-    q->p.counters = reinterpret_cast<unsigned long long*>(q->arena + PT_RAYS_CTL_BYTES);
-    q->p.exact = reinterpret_cast<uint32_t*>(q->arena + PT_RAYS_CTL_BYTES + kCtrBytes);
-    q->p.aux_words = aux_words;
-    q->p.dfs_words = std::max<uint32_t>(s->max_stack, 1u);
-    q->p.service = (uint32_t)std::min(64, std::max(1, tune_int("rays_service", PT_RAYS_SERVICE)));
-    *out = q;
-    return PT_OK;
+    return qctx_create(s, device, max_points, "max_points", out, [&](pt_featq* q, const DevScene& ds, uint32_t cus) {
+        // the lanes' aux stacks, the workgroup, the resident grid and the arena's tail: k_rays' rules (rayq.cpp)
+        const LaneWords w = lane_words(s);
+        (void)fit_block(w.aux_words, 0u, &q->block);
+        q->max_grid = cus * (2048u / q->block);
+        if (const int rc = qctx_alloc(q, PT_RAYS_CTL_BYTES, (size_t)max_points * 4u, "feature", PT_E_OOM)) return rc;
+        q->p.S = device_view(s, ds);
+        q->p.cam = make_cam(s);
+        q->p.head = reinterpret_cast<unsigned long long*>(q->arena);
+        q->p.exact_n = reinterpret_cast<uint32_t*>(q->arena + 8);
+        q->p.counters = q->counters;
+        q->p.exact = reinterpret_cast<uint32_t*>(q->arena + PT_RAYS_CTL_BYTES + kQCtrBytes);
+        q->p.aux_words = w.aux_words;
+        q->p.dfs_words = w.dfs_words;
+        q->p.service = (uint32_t)std::min(64, std::max(1, tune_int("rays_service", PT_RAYS_SERVICE)));
+        return (int)PT_OK;
+    });
 }
 
 int pt_featq_run(pt_featq* q, void* stream, uint64_t n, const float* dev_xy, pt_feature* dev_out) {
     if (!q) return fail(PT_E_INVALID, "null feature context");
-    if (n > q->max_points) return fail(PT_E_INVALID, "more points than the context's max_points");
+    if (n > q->max_items) return fail(PT_E_INVALID, "more points than the context's max_points");
     if (n == 0) return PT_OK;
     if (!dev_xy || !dev_out) return fail(PT_E_INVALID, "null position or feature buffer");
     // (the kernel reads a position as one 8-B piece and writes a record as four 16-B pieces)
@@ -125,84 +86,33 @@ int pt_featq_run(pt_featq* q, void* stream, uint64_t n, const float* dev_xy, pt_
     if (reinterpret_cast<uintptr_t>(dev_out) & 15u) return fail(PT_E_INVALID, "the feature buffer must be 16-byte aligned");
     HIP_TRY(hipSetDevice(q->dev));
     // one run at a time: the control block and the exact list are the context's
-    if (const int rc = settle(q)) return rc;
+    if (const int rc = q->t.settle()) return rc;
     pt::FeatsParams p = q->p;
     p.xy = reinterpret_cast<const pt::FeatXY*>(dev_xy);
     p.out = reinterpret_cast<pt::Feature*>(dev_out);
     p.n = (uint32_t)n;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(q->max_grid, (n + q->block - 1u) / q->block);
-    // points a wave reserves per pull of the work counter: k_rays' rule (rayq.cpp)
-    const uint64_t waves = (uint64_t)grid * (q->block / 64u);
-    p.batch = (uint32_t)std::min<uint64_t>(512u, std::max<uint64_t>(64u, n / (waves * 8u)));
-    HIP_TRY(pt_launch_feats(p, grid, q->block, static_cast<hipStream_t>(stream), q->e0, q->e1));
-    q->pending = true;
+    const RunShape sh = qctx_shape(q, n);
+    p.batch = sh.batch;
+    HIP_TRY(pt_launch_feats(p, sh.grid, q->block, static_cast<hipStream_t>(stream), q->t.e0, q->t.e1));
+    q->t.pending = true;
     return PT_OK;
 }
 
-int pt_featq_stats(pt_featq* q, pt_stats* st) {
-    if (!q || !st) return fail(PT_E_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(q->dev));
-    if (const int rc = settle(q)) return rc;
-    unsigned long long cc[PT_CTR_COPIES * PT_CTR_STRIDE];
-    HIP_TRY(hipMemcpy(cc, q->p.counters, sizeof(cc), hipMemcpyDeviceToHost));
-    unsigned long long c[8];
-    for (uint32_t k = 0; k < 8u; ++k) {
-        unsigned long long sum = 0ull;
-        for (uint32_t x = 0; x < PT_CTR_COPIES; ++x) sum += cc[PT_CTR_STRIDE * x + k];
-        c[k] = sum - q->seen[k];
-        q->seen[k] = sum;
-    }
-    memset(st, 0, sizeof(*st));
-    counter_stats(c, st);
-    st->kernel_ms = q->kernel_ms;
-    q->kernel_ms = 0.0;
-    // algorithmic bytes per counted unit, as a wavefront session reports them
-    st->node_bytes = sizeof(pt::Node);
-    st->prim_bytes = 48;
-    st->aux_bytes = PT_AUXW * sizeof(pt::AuxSL);
-    return PT_OK;
-}
+int pt_featq_stats(pt_featq* q, pt_stats* st) { return qctx_stats(q, 8u, st); }
 
-void pt_featq_free(pt_featq* q) {
-    if (!q) return;
-    (void)hipSetDevice(q->dev);
-    if (q->pending) (void)hipEventSynchronize(q->e1);   // the last run still reads the arena
-    if (q->e0) (void)hipEventDestroy(q->e0);
-    if (q->e1) (void)hipEventDestroy(q->e1);
-    (void)hipFree(q->arena);
-    delete q;
-}
+void pt_featq_free(pt_featq* q) { qctx_free(q); }
 
 int pt_features(pt_scene* s, int device, uint64_t n, const float* xy, pt_feature* out, pt_stats* stats) {
     if (!s) return fail(PT_E_INVALID, "null scene");
     if (n > 0 && (!xy || !out)) return fail(PT_E_INVALID, "null position or feature buffer");
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (n == 0) return PT_OK;
-    const uint64_t cap = std::min(n, kChunk);
-    pt_featq* q = nullptr;
-    int rc = pt_featq_create(s, device, cap, &q);
-    if (rc) return rc;
-    void* dx = nullptr;
-    void* df = nullptr;
-    auto done = [&](int code) {
-        (void)hipFree(dx);
-        (void)hipFree(df);
-        pt_featq_free(q);
-        return code;
-    };
-    if (hipMalloc(&dx, cap * sizeof(pt::FeatXY)) != hipSuccess || hipMalloc(&df, cap * sizeof(pt_feature)) != hipSuccess)
-        return done(fail(PT_E_OOM, "position / feature buffers: hipMalloc failed"));
-    for (uint64_t at = 0; at < n; at += cap) {
-        const uint64_t m = std::min(cap, n - at);
-        if (hipMemcpy(dx, xy + 2 * at, m * sizeof(pt::FeatXY), hipMemcpyHostToDevice) != hipSuccess)
-            return done(fail(PT_E_HIP, "position upload failed"));
-        if ((rc = pt_featq_run(q, nullptr, m, static_cast<const float*>(dx), static_cast<pt_feature*>(df)))) return done(rc);
-        // (the null stream orders this copy after the run)
-        if (hipMemcpy(out + at, df, m * sizeof(pt_feature), hipMemcpyDeviceToHost) != hipSuccess)
-            return done(fail(PT_E_HIP, "feature download failed"));
-    }
-    if (stats && (rc = pt_featq_stats(q, stats))) return done(rc);
-    return done(PT_OK);
+    return run_chunks<pt_featq>(
+        s, device, n, stats, {pt_featq_create, pt_featq_stats, pt_featq_free}, sizeof(pt::FeatXY), sizeof(pt_feature),
+        PT_E_OOM, "position / feature buffers: hipMalloc failed",
+        [&](void* const* d, uint64_t at, uint64_t m) { return copy_up(d[0], xy + 2 * at, m * sizeof(pt::FeatXY), "position upload"); },
+        [&](pt_featq* q, void* const* d, uint64_t m) {
+            return pt_featq_run(q, nullptr, m, static_cast<const float*>(d[0]), static_cast<pt_feature*>(d[1]));
+        },
+        [&](void* const* d, uint64_t at, uint64_t m) { return copy_down(out + at, d[1], m * sizeof(pt_feature), "feature download"); });
 }
 
 int pt_session_features(pt_session* ss, pt_feature* dev_out, uint64_t cap, pt_stats* st) {

@@ -16,16 +16,6 @@ namespace {
 
 constexpr uint32_t kGuideChunk = 1u << 22;   // guide points per feature run
 
-int settle(pt_filtq* q) {
-    if (!q->pending) return PT_OK;
-    HIP_TRY(hipEventSynchronize(q->e1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, q->e0, q->e1));
-    q->kernel_ms += ms;
-    q->pending = false;
-    return PT_OK;
-}
-
 bool opts_ok(const pt_filter_opts* o) {
     return o && pt::filter_opts_ok(o->levels, o->sigma_c, o->sigma_z, o->sigma_a, o->normal_pow2, o->layout);
 }
@@ -144,8 +134,7 @@ int pt_filtq_create(pt_scene* s, int device, uint32_t x0, uint32_t y0, uint32_t 
     if (hipSetDevice(device) != hipSuccess) return cleanup(fail(PT_E_HIP, "hipSetDevice failed"));
     if (hipMalloc(reinterpret_cast<void**>(&q->arena), n * (sizeof(pt::FilterGuide) + 2u * sizeof(uint4))) != hipSuccess)
         return cleanup(fail(PT_E_OOM, "filter buffers: hipMalloc failed"));
-    if (hipEventCreate(&q->e0) != hipSuccess || hipEventCreate(&q->e1) != hipSuccess)
-        return cleanup(fail(PT_E_HIP, "filter set-up failed"));
+    if (!q->t.create()) return cleanup(fail(PT_E_HIP, "filter set-up failed"));
     if ((rc = make_guides(q))) return cleanup(rc);
     *out = q;
     return PT_OK;
@@ -156,7 +145,7 @@ int pt_filtq_set_features(pt_filtq* q, void* stream, const pt_feature* dev_featu
     if (!dev_features) return fail(PT_E_INVALID, "null feature buffer");
     if (reinterpret_cast<uintptr_t>(dev_features) & 15u) return fail(PT_E_INVALID, "the feature buffer must be 16-byte aligned");
     HIP_TRY(hipSetDevice(q->dev));
-    if (const int rc = settle(q)) return rc;   // (the last run still reads the guides)
+    if (const int rc = q->t.settle()) return rc;   // (the last run still reads the guides)
     pt::FilterGuideParams p;
     memset(&p, 0, sizeof(p));
     p.feat = reinterpret_cast<const pt::Feature*>(dev_features);
@@ -181,7 +170,7 @@ int pt_filtq_run(pt_filtq* q, void* stream, const pt_filter_opts* opts, const fl
         return fail(PT_E_INVALID, "the input and output ranges overlap");
     HIP_TRY(hipSetDevice(q->dev));
     // one run at a time: the levels' colours are the context's
-    if (const int rc = settle(q)) return rc;
+    if (const int rc = q->t.settle()) return rc;
     const hipStream_t st = static_cast<hipStream_t>(stream);
     pt::FilterParams p;
     memset(&p, 0, sizeof(p));
@@ -192,7 +181,7 @@ int pt_filtq_run(pt_filtq* q, void* stream, const pt_filter_opts* opts, const fl
     p.thr = q->thr;
     p.w = q->w; p.h = q->h;
     p.tiles_x = tiles_x_of(q->w);
-    HIP_TRY(hipEventRecord(q->e0, st));
+    HIP_TRY(hipEventRecord(q->t.e0, st));
     const int rc = run_levels(*opts, [&](const pt::FilterLevel& lv, uint32_t in_kind, bool last, uint32_t from, uint32_t to) {
         p.lv = lv;
         p.src = colours_of(q, from);
@@ -201,19 +190,19 @@ int pt_filtq_run(pt_filtq* q, void* stream, const pt_filter_opts* opts, const fl
         return (int)PT_OK;
     });
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(q->e1, st));
-    q->pending = true;
+    HIP_TRY(hipEventRecord(q->t.e1, st));
+    q->t.pending = true;
     return PT_OK;
 }
 
 int pt_filtq_stats(pt_filtq* q, pt_stats* st) {
     if (!q || !st) return fail(PT_E_INVALID, "null argument");
     HIP_TRY(hipSetDevice(q->dev));
-    if (const int rc = settle(q)) return rc;
+    if (const int rc = q->t.settle()) return rc;
     memset(st, 0, sizeof(*st));
-    st->kernel_ms = q->kernel_ms;
+    st->kernel_ms = q->t.kernel_ms;
     st->rays = q->guide_points;
-    q->kernel_ms = 0.0;
+    q->t.kernel_ms = 0.0;
     q->guide_points = 0;
     return PT_OK;
 }
@@ -221,9 +210,7 @@ int pt_filtq_stats(pt_filtq* q, pt_stats* st) {
 void pt_filtq_free(pt_filtq* q) {
     if (!q) return;
     (void)hipSetDevice(q->dev);
-    if (q->pending) (void)hipEventSynchronize(q->e1);   // the last run still uses the arena
-    if (q->e0) (void)hipEventDestroy(q->e0);
-    if (q->e1) (void)hipEventDestroy(q->e1);
+    q->t.destroy();   // (waits: the last run still uses the arena)
     (void)hipFree(q->arena);
     delete q;
 }

@@ -239,6 +239,7 @@ _sig = {
     "pt_selftest_filter_host": (C.c_int, [C.c_uint32, C.c_uint32, _P, C.POINTER(FilterOpts), _P, _P]),
     "pt_selftest_gamma_table": (C.c_int, [_P, _P]),
     "pt_selftest_wave_plan": (C.c_int, [_P, C.POINTER(SessionOpts), C.c_uint32, C.c_char_p, C.c_size_t]),
+    "pt_selftest_fold_shape": (C.c_int, [C.c_uint32] * 4 + [C.POINTER(C.c_uint32)] * 2),
     "pt_selftest_state_slots": (C.c_int, [_P, C.POINTER(SessionOpts), C.c_uint64, _P, _P]),
     "pt_selftest_count_records": (C.c_int, [_P, C.POINTER(SessionOpts), C.c_uint64, _P, C.POINTER(C.c_uint64)]),
     "pt_selftest_count_step": (C.c_int, [C.c_uint32, C.c_uint64, _P, _P, _P, _P, C.POINTER(C.c_uint32)]),
@@ -745,9 +746,37 @@ def _addr(x):
     return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else x)
 
 
-class RayQuery:
+class _Query:
+    """What the device contexts below share: the handle's statistics and its release.  A subclass
+    names its context's pt_*_stats and pt_*_free in _stats and _free and makes self._h."""
+
+    _stats = _free = None
+
+    def stats(self):
+        """Wait for the last run; the counters and kernel time of the runs since the last call."""
+        st = Stats()
+        _check(getattr(_lib, self._stats)(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            getattr(_lib, self._free)(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class RayQuery(_Query):
     """Closest-hit queries for rays already on the device (include/pt.h ray queries): one
     context per scene and device, for runs of up to max_rays rays."""
+
+    _stats, _free = "pt_rayq_stats", "pt_rayq_free"
 
     def __init__(self, scene, device=0, max_rays=RAYS_CHUNK):
         self.scene = scene
@@ -764,29 +793,12 @@ class RayQuery:
             n = rays.numel() // 6
         _check(_lib.pt_rayq_run(self._h, stream, n, _addr(rays), _addr(hits)))
 
-    def stats(self):
-        """Wait for the last run; the counters and kernel time of the runs since the last call."""
-        st = Stats()
-        _check(_lib.pt_rayq_stats(self._h, C.byref(st)))
-        return st.as_dict()
 
-    def close(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            _lib.pt_rayq_free(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-
-class FeatureQuery:
+class FeatureQuery(_Query):
     """First-hit features for positions already on the device (include/pt.h first-hit features):
     one context per scene and device, for runs of up to max_points positions."""
+
+    _stats, _free = "pt_featq_stats", "pt_featq_free"
 
     def __init__(self, scene, max_points=FEATS_CHUNK, device=0):
         self.scene = scene
@@ -803,29 +815,12 @@ class FeatureQuery:
             n = d_xy.numel() // 2
         _check(_lib.pt_featq_run(self._h, stream, n, _addr(d_xy), _addr(d_out)))
 
-    def stats(self):
-        """Wait for the last run; the counters and kernel time of the runs since the last call."""
-        st = Stats()
-        _check(_lib.pt_featq_stats(self._h, C.byref(st)))
-        return st.as_dict()
 
-    def close(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            _lib.pt_featq_free(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-
-class FilterQuery:
+class FilterQuery(_Query):
     """The guided filter for frames already on the device (include/pt.h "guided filter"): one context
     per scene, device and window (None: the full image); it holds the window's guides."""
+
+    _stats, _free = "pt_filtq_stats", "pt_filtq_free"
 
     def __init__(self, scene, window=None, device=0):
         self.scene = scene
@@ -858,22 +853,7 @@ class FilterQuery:
     def stats(self):
         """Wait for the last run; kernel_ms of the runs and rays = the guide points traced since the
         last call."""
-        st = Stats()
-        _check(_lib.pt_filtq_stats(self._h, C.byref(st)))
-        return st.as_dict()
-
-    def close(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            _lib.pt_filtq_free(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+        return super().stats()
 
 
 def selftest_filter_host(features, radiance, w, h, **opts):
@@ -890,9 +870,11 @@ def selftest_filter_host(features, radiance, w, h, **opts):
     return out
 
 
-class PathQuery:
+class PathQuery(_Query):
     """Radiance along paths already on the device (include/pt.h batch radiance): one context per
     scene and device, for runs of up to max_paths paths."""
+
+    _stats, _free = "pt_pathq_stats", "pt_pathq_free"
 
     def __init__(self, scene, device=0, max_paths=PATHS_CHUNK):
         self.scene = scene
@@ -909,29 +891,12 @@ class PathQuery:
             n = dev_in.numel() * dev_in.element_size() // 32
         _check(_lib.pt_pathq_run(self._h, stream, n, _addr(dev_in), _addr(dev_out)))
 
-    def stats(self):
-        """Wait for the last run; the counters and kernel time of the runs since the last call."""
-        st = Stats()
-        _check(_lib.pt_pathq_stats(self._h, C.byref(st)))
-        return st.as_dict()
 
-    def close(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            _lib.pt_pathq_free(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-
-class PixelQuery:
+class PixelQuery(_Query):
     """Further samples for pixel states already on the device (include/pt.h pixel samples): one
     context per scene and device, for runs of up to max_pixels records."""
+
+    _stats, _free = "pt_pixq_stats", "pt_pixq_free"
 
     def __init__(self, scene, device=0, max_pixels=PIXELS_CHUNK):
         self.scene = scene
@@ -948,25 +913,6 @@ class PixelQuery:
         if n is None:
             n = dev_state.numel() * dev_state.element_size() // 32
         _check(_lib.pt_pixq_run(self._h, stream, n, _addr(dev_state), None if counts is None else _addr(counts), spp))
-
-    def stats(self):
-        """Wait for the last run; the counters and kernel time of the runs since the last call."""
-        st = Stats()
-        _check(_lib.pt_pixq_stats(self._h, C.byref(st)))
-        return st.as_dict()
-
-    def close(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            _lib.pt_pixq_free(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
 
 def tile_owner(t, tiles_x, world):
@@ -1011,6 +957,15 @@ def write_ppm(path, rgb):
     rgb = np.ascontiguousarray(rgb, np.uint8)
     h, w, _ = rgb.shape
     _check(_lib.pt_write_ppm(os.fsencode(path), w, h, _ptr(rgb)))
+
+
+def selftest_fold_shape(cus, per_cu, block, depth):
+    """(block, max_grid) of a batch context with fold records (PathQuery, PixelQuery) on a device of
+    `cus` compute units that hold `per_cu` workgroups of `block` threads each, at RAY_DEPTH `depth`:
+    the resident grid under the fold area's 1 GiB bound.  Needs no device and no scene."""
+    b, g = C.c_uint32(), C.c_uint32()
+    _check(_lib.pt_selftest_fold_shape(cus, per_cu, block, depth, C.byref(b), C.byref(g)))
+    return b.value, g.value
 
 
 def selftest_math(op, records, device=-1):

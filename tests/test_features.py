@@ -316,3 +316,23 @@ def test_features_and_a_render_share_the_scene(pt):
     assert st["errors"] == 0 and np.array_equal(rgb, img)
     assert np.array_equal(r.view(np.uint32), rad.view(np.uint32))
     assert qs["rays"] == 8192 and qs["errors"] == 0
+
+
+# ---- a context's statistics are those of the runs since the last call -----------------------------
+def test_stats_report_each_run_once(pt):
+    """Two equal runs of 65 positions (a wave and a lane) on one context, a stats() after each: the second
+    reports what the first did -- the context's counters run on, a stats() is the difference since
+    the last one --, and a third stats(), with no run since, no work and no time."""
+    import torch
+    xy = np.array([(k % 13 + 5.5, k // 13 + 9.5) for k in range(65)], np.float32)
+    with pt.Scene.load(U.golden_scene_path("mat_matrix_24x24x8")) as s:
+        with pt.FeatureQuery(s, max_points=65) as q:
+            d_xy, d_out = _device_buffers(torch, xy, 65)
+            q.run(d_xy, d_out, n=65)
+            a = q.stats()
+            q.run(d_xy, d_out, n=65)
+            b = q.stats()
+            c = q.stats()
+    assert a["rays"] == 65 and a["node_visits"] > 0 and a["prim_tests"] > 0 and a["kernel_ms"] > 0.0
+    assert (b["rays"], b["node_visits"], b["prim_tests"]) == (a["rays"], a["node_visits"], a["prim_tests"])
+    assert c["rays"] == 0 and c["kernel_ms"] == 0

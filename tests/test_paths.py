@@ -246,3 +246,23 @@ def test_ray_depth_0_gives_zeros_and_no_rays(pt):
         got, st = s.radiance(rec)
     assert not got.view(np.uint32).any()
     assert st["rays"] == 0 and st["errors"] == 0
+
+
+# ---- a context's statistics are those of the runs since the last call -----------------------------
+def test_stats_report_each_run_once(pt):
+    """Two equal runs of 65 paths (a wave and a lane) on one context, a stats() after each: the second
+    reports what the first did -- the context's counters run on, a stats() is the difference since
+    the last one --, and a third stats(), with no run since, no work and no time."""
+    import torch
+    with pt.Scene.load(U.golden_scene_path("mat_matrix_24x24x8")) as s:
+        rec = P.pixel_records(pt, s, 24, (5, 9, 13, 5))
+        with pt.PathQuery(s, max_paths=65) as q:
+            d_in, d_out = _device_buffers(torch, rec, 65)
+            q.run(d_in, d_out, n=65)
+            a = q.stats()
+            q.run(d_in, d_out, n=65)
+            b = q.stats()
+            c = q.stats()
+    assert a["rays"] >= 65 and a["node_visits"] > 0 and a["prim_tests"] > 0 and a["kernel_ms"] > 0.0
+    assert (b["rays"], b["node_visits"], b["prim_tests"]) == (a["rays"], a["node_visits"], a["prim_tests"])
+    assert c["rays"] == 0 and c["kernel_ms"] == 0

@@ -214,3 +214,25 @@ def test_sample_pixels_leaves_its_argument_alone(pt):
         out, st = s.sample_pixels(state, counts=np.arange(100) % 3)
     assert state.tobytes() == before and np.array_equal(out["samples"], np.arange(100) % 3)
     assert out[::3].tobytes() == state[::3].tobytes()
+
+
+# ---- a context's statistics are those of the runs since the last call -----------------------------
+def test_stats_report_each_run_once(pt):
+    """Two equal runs of 65 records (a wave and a lane) on one context, a stats() after each: the second
+    reports what the first did -- the context's counters run on, a stats() is the difference since
+    the last one --, and a third stats(), with no run since, no work and no time."""
+    import torch
+    with pt.Scene.load(U.golden_scene_path("mat_matrix_24x24x8")) as s:
+        state = s.pixel_init(X.window_xy((5, 9, 13, 5)))
+        with pt.PixelQuery(s, max_pixels=65) as q:
+            d1, d2 = device_state(pt, torch, state), device_state(pt, torch, state)   # (a run updates its states)
+            torch.cuda.synchronize()
+            q.run(d1, spp=2, n=65)
+            a = q.stats()
+            q.run(d2, spp=2, n=65)
+            b = q.stats()
+            c = q.stats()
+    assert a["samples"] == 130 and a["rays"] >= 130 and a["node_visits"] > 0 and a["prim_tests"] > 0 and a["kernel_ms"] > 0.0
+    assert (b["rays"], b["node_visits"], b["prim_tests"], b["samples"]) == \
+        (a["rays"], a["node_visits"], a["prim_tests"], a["samples"])
+    assert c["rays"] == 0 and c["samples"] == 0 and c["kernel_ms"] == 0
