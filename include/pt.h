@@ -665,6 +665,25 @@ int pt_selftest_wave_plan(pt_scene* s, const pt_session_opts* o, uint32_t cus, c
  * where one wave per compute unit still exceeds it. */
 int pt_selftest_fold_shape(uint32_t cus, uint32_t per_cu, uint32_t block, uint32_t depth, uint32_t* block_out,
                            uint32_t* grid_out);
+/* the batch engines' workgroup for lanes whose stacks take `aux_words` (the aux stack) and `dfs_words`
+ * (the exact DFS's) words, without a device: *block_aux_only as pt_rayq / pt_featq choose it (their
+ * lanes hold the aux stack only, their exact kernel's one wave the DFS stack), *block_both as pt_pathq /
+ * pt_pixq do before the fold area's bound (a lane's column holds the larger of the two): from 256
+ * threads down to 64 until the columns fit a workgroup's 64 KiB of LDS.  *fits: bit 0 the first
+ * kind accepts the stacks, bit 1 the second does (a refusal is their PT_E_SCENE). */
+int pt_selftest_fit_block(uint32_t aux_words, uint32_t dfs_words, uint32_t* block_aux_only, uint32_t* block_both,
+                          uint32_t* fits);
+/* ... for a scene's own stack words, which it also returns.  Prepares the scene if needed. */
+int pt_selftest_lane_shape(pt_scene* s, uint32_t* aux_words, uint32_t* dfs_words, uint32_t* block_aux_only,
+                           uint32_t* block_both, uint32_t* fits);
+/* a live batch context's launch shape: its workgroup, its resident grid, and the workgroups per
+ * compute unit that shape started from (pt_rayq, pt_featq: 2,048 lanes' worth; pt_pathq, pt_pixq: the
+ * kernel's occupancy).  kind names what ctx is.  Read-only. */
+#define PT_CTX_RAYQ 0u
+#define PT_CTX_FEATQ 1u
+#define PT_CTX_PATHQ 2u
+#define PT_CTX_PIXQ 3u
+int pt_selftest_ctx_shape(uint32_t kind, const void* ctx, uint32_t* block, uint32_t* max_grid, uint32_t* per_cu);
 /* per record the session slot it would land in, by the functions k_states_mark uses compiled
  * for the host: >= 0 slot, -1 in the image but not this session's, -2 outside the image or a
  * bad rng word (of a pixel that is this session's: another's record is -1 whatever it holds).

@@ -405,6 +405,7 @@ struct QueryCtx {
     unsigned char* arena = nullptr;
     unsigned long long* counters = nullptr;   // PT_CTR_COPIES x PT_CTR_STRIDE, in the arena behind the control block
     uint32_t block = 256, max_grid = 1;   // the kernel's workgroup (its lanes' stacks fit the LDS) and the resident grid
+    uint32_t per_cu = 0;   // the workgroups per compute unit the shape started from (pt_selftest_ctx_shape reports it)
     RunTimer t;
     unsigned long long seen[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // the counters at the last *_stats
 };
@@ -448,6 +449,11 @@ LaneWords lane_words(const pt_scene* s);
 // The widest workgroup, from *block down to 64 threads, whose lanes' LDS columns (pt_batch.h
 // lane_lds_bytes) fit a workgroup's LDS; false: not even 64 lanes' do (*block is 64 then)
 bool fit_block(uint32_t aux_words, uint32_t dfs_words, uint32_t* block);
+// The shape of an engine without fold records (k_rays, k_feats: the lanes hold the aux stack only, the
+// exact kernel's one wave the DFS stack): the block fit of both (PT_E_SCENE), and every workgroup a
+// compute unit can hold at 8 waves per SIMD (a workgroup that starts after the work counter has
+// passed n leaves at once); q's block, per_cu and max_grid set
+int rays_shape(QueryCtx* q, LaneWords w, uint32_t cus);
 // The resident grid of an engine with fold records (RAY_DEPTH x 16 B per resident lane): per_cu
 // workgroups on each compute unit, unless the fold area then exceeds 1 GiB -- fewer workgroups then,
 // after that narrower ones, down to one wave per compute unit; PT_E_OOM where that is still too much

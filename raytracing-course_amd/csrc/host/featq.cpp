@@ -60,8 +60,7 @@ int pt_featq_create(pt_scene* s, int device, uint64_t max_points, pt_featq** out
     return qctx_create(s, device, max_points, "max_points", out, [&](pt_featq* q, const DevScene& ds, uint32_t cus) {
         // the lanes' aux stacks, the workgroup, the resident grid and the arena's tail: k_rays' rules (rayq.cpp)
         const LaneWords w = lane_words(s);
-        (void)fit_block(w.aux_words, 0u, &q->block);
-        q->max_grid = cus * (2048u / q->block);
+        if (const int rc = rays_shape(q, w, cus)) return rc;
         if (const int rc = qctx_alloc(q, PT_RAYS_CTL_BYTES, (size_t)max_points * 4u, "feature", PT_E_OOM)) return rc;
         q->p.S = device_view(s, ds);
         q->p.cam = make_cam(s);

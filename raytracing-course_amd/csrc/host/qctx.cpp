@@ -62,6 +62,17 @@ bool fit_block(uint32_t aux_words, uint32_t dfs_words, uint32_t* block) {
     return pt::lane_lds_bytes(*block, aux_words, dfs_words) <= kMaxLds;
 }
 
+int rays_shape(QueryCtx* q, LaneWords w, uint32_t cus) {
+    // (the aux column alone always fits: aux_words <= PT_QUERY_SP_MAX, 64 lanes x 128 words = 32 KiB;
+    // the exact kernel's one wave holds the DFS stack, 64 x 4 x (dfs_words + 1) B)
+    uint32_t one_wave = 64u;
+    if (!fit_block(w.aux_words, 0u, &q->block) || !fit_block(0u, w.dfs_words, &one_wave))
+        return fail(PT_E_SCENE, "a lane's traversal stacks do not fit the LDS");
+    q->per_cu = 2048u / q->block;
+    q->max_grid = cus * q->per_cu;
+    return PT_OK;
+}
+
 int fold_shape(uint32_t cus, uint32_t per_cu, uint32_t block, uint32_t depth, GridShape* out) {
     const uint64_t lane_bytes = (uint64_t)std::max(depth, 1u) * sizeof(uint4);
     uint32_t max_grid = cus * per_cu;
@@ -85,6 +96,7 @@ int qctx_fold_shape(QueryCtx* q, LaneWords w, uint32_t cus, uint32_t depth,
     if (const int rc = fold_shape(cus, (uint32_t)per_cu, q->block, depth, &g)) return rc;
     q->block = g.block;
     q->max_grid = g.max_grid;
+    q->per_cu = (uint32_t)per_cu;
     *fold_bytes = (size_t)g.max_grid * g.block * std::max(depth, 1u) * sizeof(uint4);
     return PT_OK;
 }

@@ -15,10 +15,7 @@ extern "C" {
 int pt_rayq_create(pt_scene* s, int device, uint64_t max_rays, pt_rayq** out) {
     return qctx_create(s, device, max_rays, "max_rays", out, [&](pt_rayq* q, const DevScene& ds, uint32_t cus) {
         const LaneWords w = lane_words(s);
-        (void)fit_block(w.aux_words, 0u, &q->block);   // (k_rays' lanes hold the aux stack only)
-        // every workgroup a CU can hold at 8 waves per SIMD (a workgroup that starts after the work
-        // counter has passed n leaves at once)
-        q->max_grid = cus * (2048u / q->block);
+        if (const int rc = rays_shape(q, w, cus)) return rc;
         // the arena's tail: the exact list (max_rays words)
         if (const int rc = qctx_alloc(q, PT_RAYS_CTL_BYTES, (size_t)max_rays * 4u, "ray-query", PT_E_HIP)) return rc;
         q->p.S = device_view(s, ds);

@@ -279,6 +279,43 @@ int pt_selftest_features_host(pt_scene* s, uint64_t n, const float* xy, pt_featu
     return c[pt::CTR_ERRORS] ? fail(PT_E_INVALID, "recomputed closest hit differs from the query's") : PT_OK;
 }
 
+int pt_selftest_fit_block(uint32_t aux_words, uint32_t dfs_words, uint32_t* block_aux_only, uint32_t* block_both,
+                          uint32_t* fits) {
+    if (!block_aux_only || !block_both || !fits) return fail(PT_E_INVALID, "null argument");
+    QueryCtx rays;   // k_rays' / k_feats' rule on one compute unit: nothing but the shape is touched
+    const bool ok_rays = rays_shape(&rays, LaneWords{aux_words, dfs_words}, 1u) == PT_OK;
+    uint32_t both = 256u;   // k_paths' / k_pixels' rule (qctx_fold_shape's first step)
+    const bool ok_both = fit_block(aux_words, dfs_words, &both);
+    *block_aux_only = rays.block;
+    *block_both = both;
+    *fits = (ok_rays ? 1u : 0u) | (ok_both ? 2u : 0u);
+    return PT_OK;
+}
+
+int pt_selftest_lane_shape(pt_scene* s, uint32_t* aux_words, uint32_t* dfs_words, uint32_t* block_aux_only,
+                           uint32_t* block_both, uint32_t* fits) {
+    if (!s || !aux_words || !dfs_words) return fail(PT_E_INVALID, "null argument");
+    if (const int rc = pt_scene_prepare(s)) return rc;
+    const LaneWords w = lane_words(s);
+    *aux_words = w.aux_words;
+    *dfs_words = w.dfs_words;
+    return pt_selftest_fit_block(w.aux_words, w.dfs_words, block_aux_only, block_both, fits);
+}
+
+int pt_selftest_ctx_shape(uint32_t kind, const void* ctx, uint32_t* block, uint32_t* max_grid, uint32_t* per_cu) {
+    if (!ctx || !block || !max_grid || !per_cu) return fail(PT_E_INVALID, "null argument");
+    const QueryCtx* q = kind == PT_CTX_RAYQ    ? static_cast<const QueryCtx*>(static_cast<const pt_rayq*>(ctx))
+                        : kind == PT_CTX_FEATQ ? static_cast<const QueryCtx*>(static_cast<const pt_featq*>(ctx))
+                        : kind == PT_CTX_PATHQ ? static_cast<const QueryCtx*>(static_cast<const pt_pathq*>(ctx))
+                        : kind == PT_CTX_PIXQ  ? static_cast<const QueryCtx*>(static_cast<const pt_pixq*>(ctx))
+                                               : nullptr;
+    if (!q) return fail(PT_E_INVALID, "unknown context kind");
+    *block = q->block;
+    *max_grid = q->max_grid;
+    *per_cu = q->per_cu;
+    return PT_OK;
+}
+
 int pt_selftest_gamma_table(const pt_scene* s, float* thr256) {
     if (!s || !s->prepared || !thr256) return fail(PT_E_INVALID, "scene not prepared");
     memcpy(thr256, s->thr, sizeof(s->thr));

@@ -240,6 +240,9 @@ _sig = {
     "pt_selftest_gamma_table": (C.c_int, [_P, _P]),
     "pt_selftest_wave_plan": (C.c_int, [_P, C.POINTER(SessionOpts), C.c_uint32, C.c_char_p, C.c_size_t]),
     "pt_selftest_fold_shape": (C.c_int, [C.c_uint32] * 4 + [C.POINTER(C.c_uint32)] * 2),
+    "pt_selftest_fit_block": (C.c_int, [C.c_uint32] * 2 + [C.POINTER(C.c_uint32)] * 3),
+    "pt_selftest_lane_shape": (C.c_int, [_P] + [C.POINTER(C.c_uint32)] * 5),
+    "pt_selftest_ctx_shape": (C.c_int, [C.c_uint32, _P] + [C.POINTER(C.c_uint32)] * 3),
     "pt_selftest_state_slots": (C.c_int, [_P, C.POINTER(SessionOpts), C.c_uint64, _P, _P]),
     "pt_selftest_count_records": (C.c_int, [_P, C.POINTER(SessionOpts), C.c_uint64, _P, C.POINTER(C.c_uint64)]),
     "pt_selftest_count_step": (C.c_int, [C.c_uint32, C.c_uint64, _P, _P, _P, _P, C.POINTER(C.c_uint32)]),
@@ -966,6 +969,35 @@ def selftest_fold_shape(cus, per_cu, block, depth):
     b, g = C.c_uint32(), C.c_uint32()
     _check(_lib.pt_selftest_fold_shape(cus, per_cu, block, depth, C.byref(b), C.byref(g)))
     return b.value, g.value
+
+
+def _fit_dict(a, d, b1, b2, fits):
+    return {"aux_words": a, "dfs_words": d, "block_aux_only": b1.value, "block_both": b2.value,
+            "fits_aux_only": bool(fits.value & 1), "fits_both": bool(fits.value & 2)}
+
+
+def selftest_fit_block(aux_words, dfs_words):
+    """The batch engines' workgroup for lanes of `aux_words` aux stack words and `dfs_words` exact-DFS
+    words: block_aux_only / fits_aux_only as RayQuery and FeatureQuery choose, block_both / fits_both
+    as PathQuery and PixelQuery do before the fold area's bound.  Needs no device and no scene."""
+    b1, b2, fits = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _check(_lib.pt_selftest_fit_block(aux_words, dfs_words, C.byref(b1), C.byref(b2), C.byref(fits)))
+    return _fit_dict(aux_words, dfs_words, b1, b2, fits)
+
+
+def selftest_lane_shape(scene):
+    """selftest_fit_block for `scene`'s own stack words (returned as aux_words, dfs_words)."""
+    a, d, b1, b2, fits = (C.c_uint32() for _ in range(5))
+    _check(_lib.pt_selftest_lane_shape(scene._h, C.byref(a), C.byref(d), C.byref(b1), C.byref(b2), C.byref(fits)))
+    return _fit_dict(a.value, d.value, b1, b2, fits)
+
+
+def selftest_ctx_shape(query):
+    """(block, max_grid, per_cu) of a live RayQuery, FeatureQuery, PathQuery or PixelQuery."""
+    kind = {RayQuery: 0, FeatureQuery: 1, PathQuery: 2, PixelQuery: 3}[type(query)]
+    b, g, p = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _check(_lib.pt_selftest_ctx_shape(kind, query._h, C.byref(b), C.byref(g), C.byref(p)))
+    return b.value, g.value, p.value
 
 
 def selftest_math(op, records, device=-1):
