@@ -206,6 +206,7 @@ struct QCounts {
     uint32_t nodes, aux, ptests, planes;
 #ifdef PT_QDIAG
     uint32_t cands, passes, steps, rc_acc, rc_rej, rc_walk;
+    uint32_t aux_ranges;        // aux steps of a lane that needs q_aux_entries' range test
 #endif
 };
 
@@ -287,6 +288,21 @@ PT_HD void q_init_pre(const Ray& ray, float P, int pid, F4 pre, Query& q) {
 PT_HD void q_init(const SceneView& S, const Ray& ray, float P, int pid, Query& q) {
     q_init_pre(ray, P, pid, q_prep(S, ray), q);
 }
+
+// q_exec_aux has a general body and a shorter one for the common state of a wave (no lane in
+// a later pass or with a full list), picked by a wave-uniform test.  The host self-tests can
+// force the general body on every step (q_force_general(): the calling thread's switch, set
+// by pt_selftest_ray_intersection alone -- the render self-test's worker threads never see
+// it); device code has no such switch.
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ bool q_general_forced() { return false; }
+#else
+inline bool& q_force_general() {
+    static thread_local bool on = false;
+    return on;
+}
+inline bool q_general_forced() { return q_force_general(); }
+#endif
 
 // hidx[k] / ht[k] / hid[k] for a lane-varying k < PT_QHK: an unrolled select
 // chain.  Its default is not an element, so the optimiser cannot fold the chain
@@ -554,6 +570,55 @@ PT_HD void q_aux_next(Query& q, Mem& stk, uint32_t next) {
 #define QP_STAMP(i) (void)0
 #define QP_ARG
 #endif
+// The bookkeeping of an aux node's PT_AUXW entries, given their box tests `hit`: the first
+// entry taken is the lane's next item (`next`), the others go on its stack (`sp`).
+// RANGES: with the range test, which skips a subtree whose leaves are all decided or all
+// above a full list (`ovf`: hits were dropped, another pass follows).  Without it (for a
+// lane with lb == 0 and a list that is not full, where every entry is fresh and none lies
+// above) an entry hit is an entry taken: the same code less the test.
+template <bool RANGES, class Mem>
+PT_HD void q_aux_entries(const SceneView& S, const Query& q, Mem& stk, const F4 r[8], const bool (&hit)[PT_AUXW],
+                         uint32_t& next, uint32_t& sp, bool& ovf) {
+    // the largest listed hitting leaf when the list is full (else none): a leaf
+    // above it could only join the list to drop out again
+    const uint32_t hmax = q.hidx[PT_QHK - 1];
+    // (bookkeeping in locals and selects: the packed fields are written once, and a
+    // stack push is one store whatever the entry -- no per-entry exec-mask branches)
+#pragma unroll
+    for (int k = 0; k < PT_AUXW; ++k) {
+        // every entry's box is conservative: a reference leaf passing it is a
+        // candidate, probed next (its own slab test is decided only if one of
+        // its primitives is hit: a leaf failing it is never entered,
+        // src/bvh.cpp:188-198)
+        const uint32_t code = f2u(r[2 * k + 1].w);
+        const uint32_t rng = f2u(r[2 * k + 1].z);   // leaf: its ordinal; internal: its leaf range
+        const bool h = hit[k] && code != 0xffffffffu;
+        const bool isleaf = (code & 0x80000000u) != 0u;
+        bool take = h;
+        if constexpr (RANGES) {
+            const uint32_t lidx = code & 0x7fffffffu;
+            // a subtree is skipped when all its leaves lie below lb (decided in an
+            // earlier pass), or above the largest listed hitting leaf of a full
+            // list: it could only add hits the list would drop, so another pass follows
+            // (the entry's leaf range [rlo, rhi]: a leaf's own index, an internal entry's two
+            // ends; selects, not branches.  With the list not full hmax is 0xffffffff and
+            // nothing lies above it)
+            const uint32_t rlo = isleaf ? lidx : (rng & 0xffffu) << S.aux_rshift;
+            const uint32_t rhi = isleaf ? lidx : (rng >> 16) << S.aux_rshift;
+            const bool above = rlo > hmax;
+            const bool fresh = rhi >= q.lb;
+            ovf = ovf || (h && fresh && above);
+            take = h && fresh && !above;
+        }
+        const uint32_t item = isleaf ? (PT_LEAFQ | rng) : code;
+        const bool first = take && next == 0xffffffffu;
+        const bool push = take && !first;
+        next = first ? item : next;
+        stk.setc(sp, item, push && sp < stk.cap);
+        sp += push ? 1u : 0u;   // (past the stack's capacity: the exact DFS below)
+    }
+}
+
 // The aux-node step kind (one wide node: PT_AUXW child entries); ends in the next
 // aux item, the end of the pass (Q_DECIDE) or the exact DFS.
 template <class Mem>
@@ -588,43 +653,17 @@ PT_HD void q_exec_aux(const SceneView& S, Query& q, QCounts& C, Mem& stk, const 
         }
     }
     uint32_t next = 0xffffffffu;
-    // the largest listed hitting leaf when the list is full (else none): a leaf
-    // above it could only join the list to drop out again
-    const uint32_t hmax = q.hidx[PT_QHK - 1];
-    // (bookkeeping in locals and selects: the packed fields are written once, and a
-    // stack push is one store whatever the entry -- no per-entry exec-mask branches)
     uint32_t sp = q.sp;
     bool ovf = false;
-#pragma unroll
-    for (int k = 0; k < PT_AUXW; ++k) {
-        // every entry's box is conservative: a reference leaf passing it is a
-        // candidate, probed next (its own slab test is decided only if one of
-        // its primitives is hit: a leaf failing it is never entered,
-        // src/bvh.cpp:188-198)
-        const uint32_t code = f2u(r[2 * k + 1].w);
-        const uint32_t rng = f2u(r[2 * k + 1].z);   // leaf: its ordinal; internal: its leaf range
-        const bool h = hit[k] && code != 0xffffffffu;
-        const bool isleaf = (code & 0x80000000u) != 0u;
-        const uint32_t lidx = code & 0x7fffffffu;
-        // a subtree is skipped when all its leaves lie below lb (decided in an
-        // earlier pass), or above the largest listed hitting leaf of a full
-        // list: it could only add hits the list would drop, so another pass follows
-        // (the entry's leaf range [rlo, rhi]: a leaf's own index, an internal entry's two
-        // ends; selects, not branches.  With the list not full hmax is 0xffffffff and
-        // nothing lies above it)
-        const uint32_t rlo = isleaf ? lidx : (rng & 0xffffu) << S.aux_rshift;
-        const uint32_t rhi = isleaf ? lidx : (rng >> 16) << S.aux_rshift;
-        const bool above = rlo > hmax;
-        const bool fresh = rhi >= q.lb;
-        ovf = ovf || (h && fresh && above);
-        const bool take = h && fresh && !above;
-        const uint32_t item = isleaf ? (PT_LEAFQ | rng) : code;
-        const bool first = take && next == 0xffffffffu;
-        const bool push = take && !first;
-        next = first ? item : next;
-        stk.setc(sp, item, push && sp < stk.cap);
-        sp += push ? 1u : 0u;   // (past the stack's capacity: the exact DFS below)
-    }
+    // the range test decides something only for a lane in a later pass (lb != 0) or with a
+    // full list: a wave with no such lane runs the entries without it
+#ifdef PT_QDIAG
+    if (q.lb != 0u || q.hidx[PT_QHK - 1] != 0xffffffffu) C.aux_ranges++;
+#endif
+    if (pt_any(q.lb != 0u || q.hidx[PT_QHK - 1] != 0xffffffffu) || q_general_forced())
+        q_aux_entries<true>(S, q, stk, r, hit, next, sp, ovf);
+    else
+        q_aux_entries<false>(S, q, stk, r, hit, next, sp, ovf);
     if (ovf) q.overflow = 1u;
     if (sp > stk.cap) {
         q.phase = Q_EXACT;   // the pending items do not fit the stack: exact DFS (same result)

@@ -127,6 +127,8 @@ const Rccl& rccl() {
 //   qengine=trip      host self-tests, traversal 0 (pt_selftest_ray_intersection): the state machine in
 //                     the path engine's trips (q_run_trip: a step and aux_extra more aux-node steps,
 //                     then one q_decide)
+//   qforms=general    host self-tests (pt_selftest_ray_intersection): the general q_exec_aux body on
+//                     every step, where a wave's state would pick the short one
 //   prepstats=1       pt_scene_prepare's per-stage times on stderr
 std::string tune_str(const char* key) {
     // the single-variable switches of earlier builds are ignored now: say so once

@@ -27,6 +27,12 @@ struct HostVStore {
         idm = v[3 * k]; s1 = pt::u2f(v[3 * k + 1]); s2 = pt::u2f(v[3 * k + 2]);
     }
 };
+// the general body of q_exec_aux on this thread for the holder's life (pt_query.h)
+struct ForceGeneral {
+    const bool was;
+    explicit ForceGeneral(bool on) : was(pt::q_force_general()) { pt::q_force_general() = on; }
+    ~ForceGeneral() { pt::q_force_general() = was; }
+};
 }  // namespace
 }  // namespace pti
 
@@ -47,6 +53,11 @@ int pt_selftest_ray_intersection(pt_scene* s, int32_t traversal, uint32_t n, con
     // the state machine in the path engine's trips (q_trip), PT_TUNE aux_extra extra aux-node steps each
     const bool trip = tune_str("qengine") == "trip";
     const uint32_t aux_extra = (uint32_t)std::max(0, tune_int("aux_extra", 1));
+    // qforms=general: the general q_exec_aux body on every step of this call
+    const ForceGeneral forced(tune_str("qforms") == "general");
+#ifdef PT_QDIAG
+    uint64_t aux_steps = 0, aux_ranges = 0;
+#endif
     for (uint32_t i = 0; i < n; ++i) {
         pt::Ray r;
         r.o = pt::mk3(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]);
@@ -64,6 +75,9 @@ int pt_selftest_ray_intersection(pt_scene* s, int32_t traversal, uint32_t n, con
             if (Q.planes & 0x80000000u) return fail(PT_E_INVALID, "recomputed closest hit differs from the query's");
             C.rays++;
             C.nodes += Q.nodes; C.ptests += Q.ptests; C.planes += Q.planes; C.aux += Q.aux; C.fallbacks += ex;
+#ifdef PT_QDIAG
+            aux_steps += Q.aux; aux_ranges += Q.aux_ranges;
+#endif
         } else {
             id = pt::ray_intersection<false>(V, cfg, r, stk, h, C);
         }
@@ -75,6 +89,10 @@ int pt_selftest_ray_intersection(pt_scene* s, int32_t traversal, uint32_t n, con
         hits[5 * i + 3] = ok ? h.n.z : 0.f;
         hits[5 * i + 4] = ok ? (h.interior ? 1.f : 0.f) : 0.f;
     }
+#ifdef PT_QDIAG
+    fprintf(stderr, "qdiag: %u rays, %llu aux steps, %llu of a lane that needs the range test\n", n,
+            (unsigned long long)aux_steps, (unsigned long long)aux_ranges);
+#endif
     if (counters8) {
         uint64_t c[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // (slots CTR_RAYS .. CTR_FALLBACKS_RAY)
         c[pt::CTR_RAYS] = C.rays; c[pt::CTR_NODES] = C.nodes; c[pt::CTR_PTESTS] = C.ptests; c[pt::CTR_PLANES] = C.planes;
@@ -99,6 +117,9 @@ int pt_selftest_render_host(pt_scene* s, int32_t traversal, uint32_t x0, uint32_
     const std::string qpaths = tune_str("qstats");
     const char* qpath = qpaths.empty() ? nullptr : qpaths.c_str();
     std::vector<std::vector<std::array<uint32_t, 4>>> qlogs(nt);
+#ifdef PT_QDIAG
+    std::vector<std::array<uint64_t, 3>> qd(nt, {0, 0, 0});   // per thread: queries, aux steps, range-test steps
+#endif
     const bool coop = tune_str("qengine") == "coop";   // the cooperative engine's query (pt_coop.h)
     const bool mega = tune_str("qengine") == "mega";   // the megakernel's FAST query (k_trace<true>)
     for (uint32_t t = 0; t < nt; ++t) {
@@ -126,6 +147,7 @@ int pt_selftest_render_host(pt_scene* s, int32_t traversal, uint32_t x0, uint32_
                             cc.fallbacks += ex;
                             if (Q.planes & 0x80000000u) cc.errs |= 4u;   // recomputed hit differs (checked below)
 #ifdef PT_QDIAG
+                            qd[t][0]++; qd[t][1] += Q.aux; qd[t][2] += Q.aux_ranges;
                             if (qlog) qlog->push_back({Q.aux, Q.rc_acc | (Q.rc_rej << 16), Q.rc_walk, Q.cands | (Q.passes << 16)});
 #else
                             if (qlog) qlog->push_back({Q.aux, Q.nodes, Q.ptests | (ex << 31), 0u});
@@ -145,6 +167,14 @@ int pt_selftest_render_host(pt_scene* s, int32_t traversal, uint32_t x0, uint32_
         });
     }
     for (auto& x : th) x.join();
+#ifdef PT_QDIAG
+    {
+        uint64_t a[3] = {0, 0, 0};
+        for (auto& v : qd) for (int k = 0; k < 3; ++k) a[k] += v[k];
+        fprintf(stderr, "qdiag: %llu rays, %llu aux steps, %llu of a lane that needs the range test\n",
+                (unsigned long long)a[0], (unsigned long long)a[1], (unsigned long long)a[2]);
+    }
+#endif
     if (qpath)
         if (FILE* f = fopen(qpath, "wb")) {
             for (auto& v : qlogs) fwrite(v.data(), 16, v.size(), f);
