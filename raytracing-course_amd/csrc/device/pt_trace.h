@@ -8,11 +8,15 @@
 //   * a right child's bound is the best hit found in its left sibling's
 //     subtree if there was one, else the parent's bound -- so the bound can
 //     RISE (leaf hits are not clipped to their boxes).
-// Encoding: a stack entry is (right child | hits-found-at-push << 24); leaf
-// hits are appended to a small monotone "suffix minimum" list, so the best
-// hit inside a just-finished left subtree is the first list entry whose
-// sequence number is >= the entry's; if no hit was found there, the running
-// bound is provably unchanged (every pop inside that subtree restored it).
+// Encoding: a stack entry is the right child; `seg` is the nearest leaf hit
+// since the newest entry's push, so at that entry's pop it is the best hit of
+// the just-finished left subtree; if no hit was found there, the running
+// bound is provably unchanged (no pop inside that subtree set it).  A push
+// that finds `seg` holding a hit (the hits since the entry below it) saves
+// it in a word of its own below the new entry (flagged in the entry's bit 24),
+// and the pop folds it back: every bound the recursion carries is kept, for
+// any number of hitting leaves.  Only an entry pushed after a right turn can
+// find a hit there, which bounds the words (scene_api.cpp, max_stack).
 //
 // Integrator = src/scene.cpp:83-178 made iterative.  The reference folds
 // c_k = E_k + f_k(c_{k+1}) from the deepest vertex back; the per-vertex
@@ -40,7 +44,7 @@ struct Counts {
     uint64_t planes;      // plane tests
     uint64_t aux;         // auxiliary BVH node visits (candidate replay)
     uint64_t fallbacks;   // rays that took the exact stack DFS although replay was enabled
-    uint32_t errs;        // hit-list overflow (must stay 0; the result is then not exact)
+    uint32_t errs;        // a recomputed hit that differs from its query's (the host forms set it; must stay 0)
 };
 
 struct CamView {
@@ -58,8 +62,6 @@ PT_HD Ray camera_ray(const CamView& c, float x, float y) {
     r.d = nx * c.right + ny * c.up + 1.f * c.fwd;
     return r;
 }
-
-#define PT_HITLIST 6
 
 // ---- the reference rules every query form shares, each stated once ----------
 // a node record's box: {c.xyz, s.x}, {s.yz, first/right, count} -> center c, half-size s
@@ -119,10 +121,7 @@ template <class Stack>
 PT_HD int bvh_exact(const SceneView& S, const Ray& ray, float cb, Stack& stk, Hit& best, Counts& C) {
     int best_id = -1;
     best.t = PT_INF;
-    float ms_t[PT_HITLIST];
-    uint32_t ms_q[PT_HITLIST];
-    uint32_t msn = 0;
-    uint32_t nh = 0;
+    float seg = PT_INF;   // nearest leaf hit since the newest entry's push (PT_INF: none; a hit's t is below it)
     uint32_t sp = 0;
     uint32_t node = 0;
     for (;;) {
@@ -139,28 +138,16 @@ PT_HD int bvh_exact(const SceneView& S, const Ray& ray, float cb, Stack& stk, Hi
                 int lid;
                 leaf_first_min(S, ref, cnt, ray, lb, lid, C);
                 if (lid >= 0) {
-                    // append to the monotone suffix-minimum list
-                    uint32_t keep = 0;
-#pragma unroll
-                    for (int k = 0; k < PT_HITLIST; ++k)
-                        if ((uint32_t)k < msn && ms_t[k] < lb.t) keep = (uint32_t)k + 1u;
-                    if (keep == PT_HITLIST) {
-                        // overflow: drop the oldest entry (never seen in practice; counted)
-#pragma unroll
-                        for (int k = 0; k + 1 < PT_HITLIST; ++k) { ms_t[k] = ms_t[k + 1]; ms_q[k] = ms_q[k + 1]; }
-                        keep = PT_HITLIST - 1;
-                        C.errs |= 1u;
-                    }
-#pragma unroll
-                    for (int k = 0; k < PT_HITLIST; ++k)
-                        if ((uint32_t)k == keep) { ms_t[k] = lb.t; ms_q[k] = nh; }
-                    msn = keep + 1u;
-                    nh++;
-                    if (nh >= 255u) C.errs |= 2u;
+                    if (lb.t < seg) seg = lb.t;
                     if (lb.t < best.t) { best = lb; best_id = lid; }
                 }
             } else {
-                stk.set(sp++, ref | (nh << 24));
+                // the enclosing segment's minimum goes below the entry, in a word of its own, if there is one
+                const uint32_t outer = seg < PT_INF ? 1u : 0u;
+                stk.set(sp, f2u(seg));
+                sp += outer;
+                stk.set(sp++, ref | (outer << 24));
+                seg = PT_INF;
                 node = node + 1u;
                 descend = true;
             }
@@ -169,13 +156,12 @@ PT_HD int bvh_exact(const SceneView& S, const Ray& ray, float cb, Stack& stk, Hi
         if (sp == 0u) break;
         const uint32_t e = stk.get(--sp);
         node = e & 0x00ffffffu;
-        const uint32_t hs = e >> 24;
-        if (hs != nh) {
-            // hits inside the finished left subtree: bound = their minimum
-            bool found = false;
-#pragma unroll
-            for (int k = 0; k < PT_HITLIST; ++k)
-                if (!found && (uint32_t)k < msn && ms_q[k] >= hs) { cb = ms_t[k]; found = true; }
+        // hits inside the finished left subtree: bound = their minimum; none: the parent's bound, which
+        // `cb` still is
+        if (seg < PT_INF) cb = seg;
+        if (e >> 24) {
+            const float outer = u2f(stk.get(--sp));
+            if (outer < seg) seg = outer;
         }
     }
     return best_id;

@@ -164,7 +164,11 @@ __device__ __forceinline__ int qc_leaf_test(const SceneView& S, bool act, uint32
     lc_add(lc, LC_PTESTS, cnt != 0u);
     if (cnt) {
         Hit hh;
-        if (qc_prim_hit_rec(S, ref, b0, b1, b2, F4{b3.w, 0.f, 0.f, 0.f}, ray, hh)) { best = hh; lid = (int)ref; }
+        // (strictly below PT_INF, as leaf_first_min has it: a first primitive whose t is NaN or +inf is no hit)
+        if (qc_prim_hit_rec(S, ref, b0, b1, b2, F4{b3.w, 0.f, 0.f, 0.f}, ray, hh) && hh.t < best.t) {
+            best = hh;
+            lid = (int)ref;
+        }
     }
     for (uint32_t i = 1; __ballot(i < cnt) != 0ull; ++i) {
         lc_add(lc, LC_PTESTS, i < cnt);

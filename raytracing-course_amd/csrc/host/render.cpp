@@ -402,7 +402,7 @@ int pt_render(pt_scene* s, const pt_render_opts* opts, uint8_t* rgb, float* radi
     if (o.progress) progress_bar(S, S, last);
     agg.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (stats) *stats = agg;
-    return cleanup(agg.errors ? fail(PT_E_INVALID, "exactness guard tripped (hit list overflow)") : PT_OK);
+    return cleanup(agg.errors ? fail(PT_E_INVALID, "exactness guard tripped (a recomputed hit differs from its query's)") : PT_OK);
 }
 
 int pt_write_ppm(const char* path, uint32_t W, uint32_t H, const uint8_t* rgb) {

@@ -58,8 +58,11 @@ void build_device_layout(pt_scene* s) {
         sh.s1 = pt::F4{p.emis[0], p.emis[1], p.emis[2], pt::u2f(p.mat)};
         s->dshade[i] = sh;
     }
-    // tree depth and the stack the exact DFS needs: need(v) = max(1 + need(left), need(right))
-    std::vector<uint32_t> need(s->nodes.size(), 0), dep(s->nodes.size(), 0);
+    // tree depth and the stack words the exact DFS needs (pt_trace.h bvh_exact).  An entry is one word,
+    // and one more where hits may have been found since the entry below it was pushed, which takes a
+    // right turn in between: need(v, turned) = max(1 + turned + need(left, 0), need(right, 1)).  (A right
+    // turn costs nothing and the left turn after it two, so need(root, 0) < tree depth.)
+    std::vector<uint32_t> need(s->nodes.size(), 0), need_r(s->nodes.size(), 0), dep(s->nodes.size(), 0);
     uint32_t maxdep = 0;
     for (size_t i = 0; i < s->nodes.size(); ++i) {
         const pth::HNode& n = s->nodes[i];
@@ -68,7 +71,9 @@ void build_device_layout(pt_scene* s) {
     }
     for (size_t k = s->nodes.size(); k-- > 0;) {
         const pth::HNode& n = s->nodes[k];
-        if (n.left != 0xFFFFFFFFu) need[k] = std::max(1u + need[n.left], need[n.right]);
+        if (n.left == 0xFFFFFFFFu) continue;
+        need[k] = std::max(1u + need[n.left], need_r[n.right]);
+        need_r[k] = std::max(2u + need[n.left], need_r[n.right]);
     }
     s->tree_depth = maxdep + 1;
     s->max_stack = need.empty() ? 0 : need[0];

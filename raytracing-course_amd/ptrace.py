@@ -477,8 +477,7 @@ class Scene:
 
     # test hooks (host execution of the device traversal code; not a render path)
     def selftest_ray_intersection(self, rays, traversal=TRAVERSAL_REPLAY, check=True):
-        """check=False: a hit-list overflow (the exact DFS's counted condition: the call's error)
-        does not raise; the counters' "errors" holds it"""
+        """check=False: a counted error (the counters' "errors") does not raise"""
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         ids = np.zeros(len(rays), np.int32)
         hits = np.zeros((len(rays), 5), np.float32)

@@ -22,6 +22,7 @@ sys.path.insert(0, SCENES)
 import make_scene  # noqa: E402
 sys.path.insert(0, os.path.join(REPO, "tests"))
 import _material_scenes  # noqa: E402
+import _overlap  # noqa: E402
 
 _lock = threading.Lock()
 _cache = {}
@@ -179,8 +180,11 @@ def golden_image(name):
 def scene_path(src, gen=None):
     """Path of a scene file: a committed scene, a pinned config, or a generated variant."""
     os.makedirs(GEN, exist_ok=True)
-    if gen is None and src.startswith(_material_scenes.PREFIX):
-        text = _material_scenes.scene_text(src[len(_material_scenes.PREFIX):])
+    if gen is None and (src.startswith(_material_scenes.PREFIX) or src.startswith(_overlap.PREFIX)):
+        if src.startswith(_overlap.PREFIX):
+            text = _overlap.scene_text(src)
+        else:
+            text = _material_scenes.scene_text(src[len(_material_scenes.PREFIX):])
         out = os.path.join(GEN, "%s_%s.txt" % (src.replace(":", "_"), md5(text.encode())[:8]))
         with _lock:
             if not os.path.exists(out):

@@ -18,6 +18,9 @@ Outputs (all little-endian):
   --images NAME...   add / refresh the named image fixtures in the existing manifest
   --rays NAME...     add / refresh the named ray fixtures (RAYS: our own rays through the
                      reference's two intersection calls) in the existing manifest
+  a NAME "overlap:<family>:<seed>[:<n>]" (tests/_overlap.py; "overlap:all": every one it lists) records that
+  generated scene: --rays its ray set as trav_overlap_<...>.bin, --images its 16 x 12 x 2 spp frame.  The
+  CPU restatement must answer every recorded ray, and render every recorded frame, as the reference does.
 """
 import hashlib
 import json
@@ -32,6 +35,7 @@ sys.path.insert(0, os.path.join(REPO, "scenes"))
 import make_scene  # noqa: E402
 sys.path.insert(0, os.path.join(REPO, "tests"))
 import _material_scenes  # noqa: E402
+import _overlap  # noqa: E402
 
 REF = os.path.join(REPO, "oracle", "_ref")
 SCENES = os.path.join(REPO, "scenes")
@@ -125,6 +129,11 @@ def md5f(path):
 
 def scene_file(tmp, src, gen):
     """Return a path to the scene text for fixture generation."""
+    if src.startswith(_overlap.PREFIX):
+        out = os.path.join(tmp, src.replace(":", "_") + ".txt")
+        with open(out, "w") as f:
+            f.write(_overlap.scene_text(src))
+        return out
     if src.startswith(_material_scenes.PREFIX):
         out = os.path.join(tmp, src.replace(":", "_") + ".txt")
         with open(out, "w") as f:
@@ -204,6 +213,74 @@ def record_rays(harness, tmp, name):
     return {"scene": src, "rays": TRAV_RAYS, "md5": md5f(p), "scene_md5": md5f(sc), "rays_md5": md5f(rf)}
 
 
+def _tests_util():
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import _util as U
+    return U
+
+
+def record_overlap_rays(harness, tmp, src):
+    """An overlap ray fixture: the source's ray set (tests/_overlap.py RAY_FIXTURES) through the reference's
+    two calls; the restatement must give the reference's RayIntersection answers, bit for bit."""
+    import numpy as np
+    U = _tests_util()
+    sc = scene_file(tmp, src, None)
+    o = U.OracleScene(sc)
+    rays = _overlap.ray_set(src, o, *_overlap.RAY_FIXTURES[src])
+    assert rays.dtype == "float32" and len(rays) <= 2048
+    name = _overlap.fixture_name(src)
+    rf = os.path.join(tmp, name + "_rays.f32")
+    rays.tofile(rf)
+    p = os.path.join(HERE, "trav_%s.bin" % name)
+    subprocess.check_call([harness, "rays", sc, rf, p])
+    assert os.path.getsize(p) == len(rays) * 72 <= 294912
+    got_rays, ((ids, f, inter), _) = U.read_trav(name)
+    assert np.array_equal(got_rays.view(np.uint32), rays.view(np.uint32))
+    oid, oh = o.ray_intersection(rays)
+    hit = ids != -1
+    assert np.array_equal(oid, ids), src + ": restatement ids differ"
+    assert np.array_equal(oh[hit, :4].view(np.uint32), f[hit].view(np.uint32)), src + ": restatement hits differ"
+    assert np.array_equal(oh[hit, 4] != 0, inter[hit] != 0), src + ": restatement interior flags differ"
+    print("rays", name, md5f(p), "%d hits of %d" % (hit.sum(), len(rays)))
+    return {"scene": src, "rays": len(rays), "md5": md5f(p), "scene_md5": md5f(sc), "rays_md5": md5f(rf)}
+
+
+def render_overlap_image(harness, tmp, src):
+    """An overlap image fixture: the reference's frame and radiance; the restatement must give both (NaN
+    radiance at the reference's positions, whatever the NaN's sign: _overlap.same_but_nan_signs)."""
+    import numpy as np
+    U = _tests_util()
+    name = _overlap.fixture_name(src)
+    sc = scene_file(tmp, src, None)
+    ppm = os.path.join(HERE, "img_%s.ppm" % name)
+    radf = os.path.join(HERE, "rad_%s.f32" % name)
+    subprocess.check_call([harness, "render", sc, ppm, radf])
+    cli_ppm = os.path.join(tmp, name + "_cli.ppm")
+    subprocess.check_call([os.path.join(REF, "raytracing_hw5"), sc, cli_ppm], stdout=subprocess.DEVNULL)
+    assert md5f(cli_ppm) == md5f(ppm), src
+    rgb, rad, ctr = U.OracleScene(sc).render()
+    ref_rad = np.fromfile(radf, np.float32).reshape(rad.shape)
+    assert _overlap.same_but_nan_signs(rad, ref_rad), src + ": restatement radiance differs"
+    assert np.array_equal(rgb, U.read_ppm(ppm)), src + ": restatement image differs"
+    n_nan = int(np.isnan(ref_rad).sum())
+    print("image", name, md5f(ppm), "%d NaN floats" % n_nan, ctr["rays"], "rays")
+    return {"scene": src, "gen": None, "window": None, "ppm_md5": md5f(ppm), "rad_md5": md5f(radf),
+            "scene_md5": md5f(sc), "rays": int(ctr["rays"]), "nan_floats": n_nan}
+
+
+def overlap_section(manifest):
+    """the overlap fixtures' own part of the manifest: the batteries over "images" and "trav" compare bit for
+    bit, which flat's NaNs do not allow, and these scenes are guarded before they reach a device"""
+    return manifest.setdefault("overlap", {"rays": {}, "images": {}})
+
+
+def overlap_names(names, table):
+    out = []
+    for n in names:
+        out += list(table) if n == "overlap:all" else [n]
+    return out
+
+
 def render_deep(harness, tmp, name):
     """A DEEP fixture: the reference's window + the restatement's ray count."""
     entry = render_image(harness, tmp, name, DEEP)
@@ -235,8 +312,11 @@ def main():
         with open(os.path.join(HERE, "manifest.json")) as f:
             manifest = json.load(f)
         with tempfile.TemporaryDirectory() as tmp:
-            for name in sys.argv[2:]:
-                manifest["images"][name] = render_image(harness, tmp, name)
+            for name in overlap_names(sys.argv[2:], _overlap.IMAGE_FIXTURES):
+                if name.startswith(_overlap.PREFIX):
+                    overlap_section(manifest)["images"][_overlap.fixture_name(name)] = render_overlap_image(harness, tmp, name)
+                else:
+                    manifest["images"][name] = render_image(harness, tmp, name)
         with open(os.path.join(HERE, "manifest.json"), "w") as f:
             json.dump(manifest, f, indent=1, sort_keys=True)
         return 0
@@ -244,8 +324,11 @@ def main():
         with open(os.path.join(HERE, "manifest.json")) as f:
             manifest = json.load(f)
         with tempfile.TemporaryDirectory() as tmp:
-            for name in sys.argv[2:]:
-                manifest["trav"][name] = record_rays(harness, tmp, name)
+            for name in overlap_names(sys.argv[2:], _overlap.RAY_FIXTURES):
+                if name.startswith(_overlap.PREFIX):
+                    overlap_section(manifest)["rays"][_overlap.fixture_name(name)] = record_overlap_rays(harness, tmp, name)
+                else:
+                    manifest["trav"][name] = record_rays(harness, tmp, name)
         with open(os.path.join(HERE, "manifest.json"), "w") as f:
             json.dump(manifest, f, indent=1, sort_keys=True)
         return 0
