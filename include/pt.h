@@ -629,6 +629,23 @@ int pt_selftest_ray_intersection(pt_scene* s, int32_t traversal, uint32_t n, con
                                  float* hits, uint64_t* counters8);
 int pt_selftest_render_host(pt_scene* s, int32_t traversal, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                             uint32_t spp, float* radiance);
+/* The query's decision step (pt_query.h q_decide) against the self-test's own plain loop
+ * over the hit list, on n seeded decision states (ne <= nh <= PT_QHK, sorted lists, thresholds
+ * and t's on both sides of the bounds, both values of overflow, lists full of entered hits):
+ * out3 = {states, states with a slot to examine, states whose Query differs in any byte}.
+ * Needs no GPU. */
+int pt_selftest_decide(uint64_t seed, uint64_t n, uint64_t* out3);
+/* the same n states after the decision: device < 0 the host's plain loop, device >= 0 q_decide in
+ * a kernel of its own on that device, 64 consecutive states to a wave.  states (cap bytes; may be
+ * NULL) takes n records of *state_bytes bytes each; counts (may be NULL) takes 4 + PT_QHK (= 10)
+ * values by the plain loop: the states that left to a leaf check, with the pass done, to another
+ * pass, to the exact DFS, then per slot the states whose last examined slot it was. */
+int pt_selftest_decide_states(int device, uint64_t seed, uint64_t n, void* states, uint64_t cap, uint64_t* counts,
+                              uint32_t* state_bytes);
+/* the query blob's wide aux entries against the host-form array (pt_query.h: the last two words
+ * ready-made): out5 = {entries, empty, leaf, internal, entries whose words differ from what the
+ * host form's code, range and leaf ordinal give}.  Prepares the scene if needed.  Needs no GPU. */
+int pt_selftest_aux_words(pt_scene* s, uint64_t* out5);
 /* n batch radiance records on the host: trace_path_with over the query state machine run to
  * completion, as pt_selftest_render_host runs a pixel's samples.  Fills out (rgb, and each path's
  * rays) and counters8: the totals of rays, nodes, primitive tests, plane tests, errors, aux

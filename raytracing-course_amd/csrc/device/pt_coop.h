@@ -106,15 +106,15 @@ PT_HD int qc_run(const SceneView& S, const Ray& ray, float P, int pid, F4 pre, M
         for (uint32_t k = 0; k < PT_AUXW; ++k) {
             const uint32_t o = S.o_aux + (node * PT_AUXW + k) * (uint32_t)sizeof(AuxSL);
             const F4 ea = blob_piece(S, o), eb = blob_piece(S, o + 16u);
-            const uint32_t code = f2u(eb.w);
-            if (code == 0xffffffffu) continue;
+            const uint32_t item = f2u(eb.w);   // (pt_query.h: child node, or PT_LEAFQ | ordinal)
+            if (item == 0xffffffffu) continue;
             const bool h = aux_entry_hit(ea, eb, ray, inv, oinv, pre.w);
             if (!h) continue;
-            if (!(code & 0x80000000u)) {
-                M.set(sp++, code);
+            if (!(item & PT_LEAFQ)) {
+                M.set(sp++, item);
                 continue;
             }
-            const uint32_t c = code & 0x7fffffffu;
+            const uint32_t c = f2u(eb.z);      // a leaf entry's reference leaf
             const Node nd = S.nodes[c];
             C.nodes++;
             if (!qc_slab_hit(nd, ray, inv, par)) continue;

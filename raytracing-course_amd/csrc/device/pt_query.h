@@ -47,11 +47,14 @@ namespace pt {
 #endif
 
 // Query-blob form of a wide aux entry (32 B, the AuxSL slot): two boxes in
-// binary16, each rounded outward, then {range, code}:
+// binary16, each rounded outward, then the entry's last two words ready-made for the step
+// (encode_aux_entries in host/scene_api.cpp; the scene is prepared once):
 //   w0..w2: the subtree's own box  (lo.x | lo.y << 16, lo.z | hi.x << 16, hi.y | hi.z << 16)
 //   w3..w5: the subtree's hit region (same packing; +-inf halves: unbounded)
-//   w6: internal entry -- its leaf range; leaf entry -- the leaf's bundle ordinal
-//   w7: code (internal child node, 0x80000000 | reference leaf, 0xffffffff empty)
+//   w6: internal entry -- its packed leaf range; leaf entry -- its reference leaf index
+//   w7: the item exactly as the aux pass takes or pushes it: internal entry -- its child node,
+//       leaf entry -- PT_LEAFQ | the leaf's bundle ordinal, 0xffffffff empty (no leaf item
+//       equals that: the host refuses such an ordinal)
 // A reference leaf matters only if its own box is crossed (else it is never
 // entered) AND one of its primitives is hit, which can only happen inside its
 // hit region (host/scene_api.cpp leaf_hit_region: a plain triangle is only ever hit
@@ -90,11 +93,12 @@ PT_HD bool aux_entry_hit(const F4& ea, const F4& eb, const Ray& ray, f3 inv, f3 
 }
 
 // wide aux entry, host form (AuxSL, 32 B; the array k_wcamera's costly-class test
-// reads): a = {lo.xyz, hi.x}, b = {hi.y, hi.z, range, code} with the own box in f32;
-// the query blob holds the dual binary16 form above with the same range and code:
+// reads): a = {lo.xyz, hi.x}, b = {hi.y, hi.z, range, code} with the own box in f32 and
+// code = internal child node, 0x80000000 | reference leaf, or 0xffffffff (empty);
+// the query blob holds the dual binary16 form above, an internal entry with the same range and code:
 //   internal entry: range = (max reference leaf of the subtree >> S, rounded up) << 16 | (min >> S)
 //   (S = SceneView::aux_rshift; annotate_aux_ranges in host/aux_bvh.cpp)
-//   leaf entry (code = 0x80000000 | reference leaf): range = the leaf's ordinal (its bundle)
+//   leaf entry: the host form's range is unused; the blob form holds {reference leaf, item}
 // stackless auxiliary node (32 B):
 //   internal: a = {lo.x, lo.y, lo.z, hi.x}, b = {hi.y, hi.z, u32 skip, 0xffffffff}
 //   leaf:     a = {c.x, c.y, c.z, s.x},     b = {s.y, s.z, u32 skip (= own index + 1), u32 reference leaf}
@@ -400,6 +404,10 @@ PT_HD void q_entered(Query& q) {
 // first case: lo = min(P, recorded hits) = min(P, bt) >= the threshold the probe
 // computed, q_leaf_accept_t) are entered here; the first other one gets the leaf
 // check (R_CAND), or the pass is done.
+// (A slot-indexed form -- slot j examined in iteration j by the lanes whose ne is j, selects
+// and a wave-uniform exit -- was measured and is not here: profiles/r29_decide.  The host and
+// device self-tests, pt_selftest_decide and k_selftest_decide, hold whatever form this
+// function takes to the plain statement of this loop in host/selftest.cpp.)
 PT_HD void q_decide(Query& q) {
 #pragma unroll 1
     while (q.ne < q.nh) {
@@ -590,13 +598,13 @@ PT_HD void q_aux_entries(const SceneView& S, const Query& q, Mem& stk, const F4 
         // candidate, probed next (its own slab test is decided only if one of
         // its primitives is hit: a leaf failing it is never entered,
         // src/bvh.cpp:188-198)
-        const uint32_t code = f2u(r[2 * k + 1].w);
-        const uint32_t rng = f2u(r[2 * k + 1].z);   // leaf: its ordinal; internal: its leaf range
-        const bool h = hit[k] && code != 0xffffffffu;
-        const bool isleaf = (code & 0x80000000u) != 0u;
+        const uint32_t item = f2u(r[2 * k + 1].w);   // the entry's item, ready-made (0xffffffff: empty)
+        const bool h = hit[k] && item != 0xffffffffu;
         bool take = h;
         if constexpr (RANGES) {
-            const uint32_t lidx = code & 0x7fffffffu;
+            const uint32_t rng = f2u(r[2 * k + 1].z);   // internal: its leaf range; leaf: its reference
+            const bool isleaf = (item >> 31) != 0u;     // index (lidx)
+            const uint32_t lidx = rng;
             // a subtree is skipped when all its leaves lie below lb (decided in an
             // earlier pass), or above the largest listed hitting leaf of a full
             // list: it could only add hits the list would drop, so another pass follows
@@ -610,7 +618,6 @@ PT_HD void q_aux_entries(const SceneView& S, const Query& q, Mem& stk, const F4 
             ovf = ovf || (h && fresh && above);
             take = h && fresh && !above;
         }
-        const uint32_t item = isleaf ? (PT_LEAFQ | rng) : code;
         const bool first = take && next == 0xffffffffu;
         const bool push = take && !first;
         next = first ? item : next;

@@ -103,4 +103,6 @@ PT_HD void math_one(uint32_t op, uint64_t i, const void* in, void* out, const fl
 #if defined(__HIPCC__) || defined(__HIP_PLATFORM_AMD__)
 hipError_t pt_launch_selftest_math(uint32_t op, uint64_t n, const void* in, void* out, const float* thr,
                                    uint32_t rng_n, hipStream_t s);
+// q_decide (pt_query.h) on n Query records in device memory, in place, a record per lane
+hipError_t pt_launch_selftest_decide(uint64_t n, void* states, hipStream_t s);
 #endif

@@ -403,7 +403,7 @@ __device__ int qc_team(const SceneView& S, const QcScene& Q, QcTeamLds<T>& L, bo
                 const bool inner = h && (code & 0x80000000u) == 0u;
                 const unsigned long long mi = __ballot(inner) & tmask, ml = __ballot(leaf) & tmask;
                 if (inner) L.stk[ns + lanes_below(mi)] = code;
-                if (leaf) L.cand[nc + lanes_below(ml)] = f2u(eb[j].z);   // (a leaf entry's range: its bundle)
+                if (leaf) L.cand[nc + lanes_below(ml)] = code & ~PT_LEAFQ;   // (a leaf entry's item: PT_LEAFQ | its bundle)
                 ns += (uint32_t)__popcll(mi);
                 nc += (uint32_t)__popcll(ml);
             }
@@ -507,7 +507,7 @@ __device__ int qc_pool(const SceneView& S, const QcScene& Q, QcPoolLds<T>& W, Qc
         const bool inner = h && (code & 0x80000000u) == 0u;
         const unsigned long long mi = __ballot(inner), ml = __ballot(leaf);
         if (inner) W.stk[ns + lanes_below(mi)] = ch << QcPoolLds<T>::SH | code;
-        if (leaf) W.cand[nc + lanes_below(ml)] = ch << QcPoolLds<T>::SH | f2u(eb.z);   // (a leaf entry's range: its bundle)
+        if (leaf) W.cand[nc + lanes_below(ml)] = ch << QcPoolLds<T>::SH | (code & ~PT_LEAFQ);   // (a leaf entry's item: PT_LEAFQ | its bundle)
         ns += (uint32_t)__popcll(mi);
         nc += (uint32_t)__popcll(ml);
     }

@@ -178,7 +178,8 @@ uint32_t f16_out(float x, bool up) {
 }
 
 // The query blob's form of the wide aux entries (pt_query.h PT_LEAF_MARGIN):
-// own box and hit region, both binary16 rounded outward, then {range, code}.
+// own box and hit region, both binary16 rounded outward, then the two words the step reads
+// ready-made (internal: {leaf range, child node}; leaf: {reference leaf, PT_LEAFQ | ordinal}).
 // A leaf's hit region is leaf_hit_region's box, or unbounded; an internal
 // entry's is the union over its child node's entries (children follow their
 // parent in the wide tree's numbering).
@@ -234,7 +235,14 @@ void encode_aux_entries(pt_scene* s, std::vector<pt::AuxSL>& aux) {
             }
             coarse += c ? 1u : 0u;
         }
-        const uint32_t range = pt::f2u(e.b.z), code = pt::f2u(e.b.w);
+        // the last two words ready-made: an internal entry keeps {leaf range, child node}, a leaf
+        // entry (b.z = its bundle ordinal, build_query_blob) holds {reference leaf, its item}
+        uint32_t range = pt::f2u(e.b.z), code = pt::f2u(e.b.w);
+        if (code & 0x80000000u) {
+            const uint32_t ordinal = range;
+            range = code & 0x7FFFFFFFu;
+            code = PT_LEAFQ | ordinal;
+        }
         // {lo.x, lo.y}, {lo.z, hi.x}, {hi.y, hi.z} per box
         e.a = pt::F4{pt::u2f(h[0] | h[1] << 16), pt::u2f(h[2] | h[3] << 16), pt::u2f(h[4] | h[5] << 16),
                      pt::u2f(h[6] | h[7] << 16)};
@@ -306,6 +314,8 @@ void build_query_blob(pt_scene* s, const std::function<void(const char*)>& tick)
         const uint32_t leaf = code & 0x7FFFFFFFu;
         if (leaf >= s->dnodes.size() || (pt::f2u(s->dnodes[leaf].b.w) & 0x80000000u) || seen[leaf]++)
             throw std::runtime_error("aux leaf entry names an internal node or a leaf twice");
+        // (the blob form's leaf item, PT_LEAFQ | ordinal, must not read as an empty entry)
+        if (leaves.size() >= 0x7FFFFFFFull) throw std::runtime_error("too many aux leaves for a leaf item");
         e.b.z = pt::u2f((uint32_t)leaves.size());
         leaves.push_back(leaf);
     }

@@ -33,6 +33,72 @@ struct ForceGeneral {
     explicit ForceGeneral(bool on) : was(pt::q_force_general()) { pt::q_force_general() = on; }
     ~ForceGeneral() { pt::q_force_general() = was; }
 };
+// q_decide stated as the plain loop over the list, apart from pt_query.h's text: the reference
+// pt_selftest_decide holds q_decide to, on the host and on the device, whatever form it takes
+// there (profiles/r29_decide measured a slot-indexed one).  Host only.
+void q_decide_loop(pt::Query& q) {
+    while (q.ne < q.nh) {
+        q.cand = pt::q_sel(q.hidx, q.ne, 0xffffffffu);
+        if (!(fminf(q.P, q.bt) >= pt::q_sel(q.hacc, q.ne, PT_INF))) {
+            q.walk = pt::R_CAND;
+            q.phase = pt::Q_REPLAY;
+            return;
+        }
+        pt::q_record_entered(q);
+    }
+    pt::q_pass_done(q);
+}
+// n seeded decision states (a lane in phase Q_DECIDE): ne <= nh <= PT_QHK, hidx sorted with
+// 0xffffffff in the empty slots, the t's, thresholds, P and bt from a few values and their
+// neighbours, so that ties and +inf are common and hacc lies on both sides of min(P, bt);
+// overflow takes both values, and one state in 32 has a list full of entered hits with
+// overflow set (the Q_EXACT exit)
+struct DecideStates {
+    uint64_t x;
+    explicit DecideStates(uint64_t seed) : x(seed * 0x9e3779b97f4a7c15ull + 0x2545f4914f6cdd1dull) {}
+    uint32_t rnd() {   // xorshift64*
+        x ^= x >> 12; x ^= x << 25; x ^= x >> 27;
+        return (uint32_t)((x * 0x2545f4914f6cdd1dull) >> 32);
+    }
+    float val() {
+        static const float base[8] = {0.5f, 1.f, 1.f, 2.f, 3.5f, PT_INF, INFINITY, 0.f};
+        const float v = base[rnd() & 7u];
+        const uint32_t k = rnd() % 5u;   // the value, a neighbour, or its negative
+        return k == 0u ? nextafterf(v, INFINITY) : k == 1u ? nextafterf(v, -INFINITY) : k == 2u ? -v : v;
+    }
+    pt::Query next() {
+        pt::Query q;
+        memset(&q, 0, sizeof(q));
+        const bool full = (rnd() & 31u) == 0u;
+        const uint32_t nh = full ? (uint32_t)PT_QHK : rnd() % (PT_QHK + 1u);
+        const uint32_t ne = full ? nh : (rnd() & 3u) ? 0u : rnd() % (nh + 1u);
+        uint32_t idx = rnd() % 1000u;
+        q.lb = idx;
+        for (uint32_t k = 0; k < PT_QHK; ++k) {
+            idx += 1u + rnd() % 50u;
+            q.hidx[k] = k < nh ? idx : 0xffffffffu;
+            q.ht[k] = val();
+            q.hacc[k] = (rnd() & 3u) ? val() : (rnd() & 1u) ? INFINITY : -INFINITY;
+            q.hid[k] = (int)(rnd() % 100000u);
+            if (k + 1u == ne) q.lb = idx + 1u;
+        }
+        q.nh = nh;
+        q.ne = ne;
+        q.P = val();
+        q.bt = (rnd() & 1u) ? PT_INF : val();
+        q.res_t = val();
+        q.res_id = (int)(rnd() % 100000u) - 1;
+        q.phase = pt::Q_DECIDE;
+        q.walk = rnd() % 3u;
+        q.overflow = full ? 1u : rnd() & 1u;
+        q.par = rnd() & 1u;
+        q.sp = rnd() & 127u;
+        q.node = rnd();
+        q.cand = rnd();
+        q.li = rnd();
+        return q;
+    }
+};
 }  // namespace
 }  // namespace pti
 
@@ -102,6 +168,94 @@ int pt_selftest_ray_intersection(pt_scene* s, int32_t traversal, uint32_t n, con
     // the exact DFS alone on this stack: it must have stayed within the words the device forms give it
     if (traversal == PT_TRAVERSAL_EXACT && stk.v.size() > std::max<uint32_t>(s->max_stack, 1u))
         return fail(PT_E_INVALID, "the exact DFS used more stack words than max_stack");
+    return PT_OK;
+}
+
+int pt_selftest_decide(uint64_t seed, uint64_t n, uint64_t* out3) {
+    if (!out3) return fail(PT_E_INVALID, "null argument");
+    // q_decide_loop is the reference: q_decide must agree on every state in every byte of the Query
+    DecideStates gen(seed);
+    uint64_t examined = 0, bad = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const pt::Query q = gen.next();
+        pt::Query a = q, b = q;
+        q_decide_loop(a);
+        pt::q_decide(b);
+        if (memcmp(&a, &b, sizeof(a))) bad++;
+        if (q.ne < q.nh) examined++;
+    }
+    out3[0] = n;
+    out3[1] = examined;
+    out3[2] = bad;
+    return PT_OK;
+}
+
+int pt_selftest_decide_states(int device, uint64_t seed, uint64_t n, void* states, uint64_t cap, uint64_t* counts,
+                              uint32_t* state_bytes) {
+    if (state_bytes) *state_bytes = (uint32_t)sizeof(pt::Query);
+    if (n == 0) return PT_OK;
+    if (n > (1ull << 24)) return fail(PT_E_INVALID, "more than 2^24 states");
+    if (states && cap < n * sizeof(pt::Query)) return fail(PT_E_INVALID, "state buffer too small");
+    std::vector<pt::Query> st((size_t)n);
+    DecideStates gen(seed);
+    uint64_t c[4 + PT_QHK] = {0};
+    for (uint64_t i = 0; i < n; ++i) {
+        const pt::Query q = gen.next();
+        pt::Query a = q;
+        q_decide_loop(a);
+        // the exit, and the last slot the loop examined (none: the lane came with ne == nh)
+        c[a.phase == pt::Q_REPLAY ? 0 : a.phase == pt::Q_DONE ? 1 : a.phase == pt::Q_AUX ? 2 : 3]++;
+        if (a.phase == pt::Q_REPLAY) c[4 + a.ne]++;
+        else if (a.ne > q.ne) c[4 + a.ne - 1u]++;
+        st[(size_t)i] = device < 0 ? a : q;
+    }
+    if (counts) memcpy(counts, c, sizeof(c));
+    if (device >= 0) {
+        if (const int rc = check_device(device)) return rc;
+        HIP_TRY(hipSetDevice(device));
+        void* buf = nullptr;
+        const size_t bytes = (size_t)n * sizeof(pt::Query);
+        HIP_TRY(hipMalloc(&buf, bytes));
+        hipError_t e = hipMemcpy(buf, st.data(), bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = pt_launch_selftest_decide(n, buf, nullptr);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipMemcpy(st.data(), buf, bytes, hipMemcpyDeviceToHost);
+        (void)hipFree(buf);
+        if (e != hipSuccess) return fail(PT_E_HIP, std::string("pt_selftest_decide_states: ") + hipGetErrorString(e));
+    }
+    if (states) memcpy(states, st.data(), (size_t)n * sizeof(pt::Query));
+    return PT_OK;
+}
+
+int pt_selftest_aux_words(pt_scene* s, uint64_t* out5) {
+    if (!s || !out5) return fail(PT_E_INVALID, "null argument");
+    if (const int rc = pt_scene_prepare(s)) return rc;
+    // every entry of the blob's aux section against the host-form array: the item (w7) and the
+    // leaf index / range (w6) the former {range, code} pair gave, and the ordinal against the
+    // bundle it names (its header holds the reference leaf)
+    const size_t n = s->auxsl.size();
+    if (s->blob.size() * 16 < (size_t)s->o_aux + n * sizeof(pt::AuxSL)) return fail(PT_E_INVALID, "no aux section");
+    const pt::AuxSL* blob = reinterpret_cast<const pt::AuxSL*>(reinterpret_cast<const unsigned char*>(s->blob.data()) + s->o_aux);
+    uint64_t empty = 0, leaf = 0, inner = 0, bad = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t code = pt::f2u(s->auxsl[i].b.w), range = pt::f2u(s->auxsl[i].b.z);
+        const uint32_t w6 = pt::f2u(blob[i].b.z), w7 = pt::f2u(blob[i].b.w);
+        if (code == 0xffffffffu) {
+            empty++;
+            if (w7 != 0xffffffffu) bad++;
+        } else if (code & 0x80000000u) {
+            // the old formula: item = PT_LEAFQ | rng, lidx = code & 0x7fffffff, with rng the leaf's
+            // ordinal: leaves are numbered in the array's order, and bundle `ordinal` holds the leaf
+            const uint32_t ord = (uint32_t)leaf++;
+            const size_t bo = (size_t)s->o_bundle / 16 + 6u * (size_t)ord + 3u;
+            const bool named = bo < s->blob.size() && pt::f2u(s->blob[bo].x) == (code & 0x7fffffffu);
+            if (w7 != (PT_LEAFQ | ord) || w7 == 0xffffffffu || w6 != (code & 0x7fffffffu) || !named) bad++;
+        } else {
+            inner++;
+            if (w7 != code || w6 != range) bad++;
+        }
+    }
+    out5[0] = n; out5[1] = empty; out5[2] = leaf; out5[3] = inner; out5[4] = bad;
     return PT_OK;
 }
 

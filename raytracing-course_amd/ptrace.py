@@ -249,6 +249,10 @@ _sig = {
     "pt_selftest_refine_plan": (C.c_int, [_P, C.POINTER(SessionOpts), C.c_uint64, _P, _P, C.POINTER(RefineOpts), _P, _P,
                                           C.POINTER(RefineResult)]),
     "pt_selftest_math": (C.c_int, [C.c_int, C.c_uint32, C.c_uint64, _P, _P]),
+    "pt_selftest_decide": (C.c_int, [C.c_uint64, C.c_uint64, _P]),
+    "pt_selftest_decide_states": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, _P, C.c_uint64, _P,
+                                            C.POINTER(C.c_uint32)]),
+    "pt_selftest_aux_words": (C.c_int, [_P, _P]),
 }
 for _name, (_res, _args) in _sig.items():
     _f = getattr(_lib, _name)
@@ -1012,6 +1016,40 @@ def selftest_math(op, records, device=-1):
         out = np.zeros(len(records), dout)
     _check(_lib.pt_selftest_math(device, code, len(records), _ptr(records), _ptr(out)))
     return out
+
+
+def selftest_decide(seed, n):
+    """pt_selftest_decide: q_decide against the plain loop on n seeded decision states, on the
+    host.  Returns {"states", "examined", "mismatches"}."""
+    out = np.zeros(3, np.uint64)
+    _check(_lib.pt_selftest_decide(seed, n, _ptr(out)))
+    return {"states": int(out[0]), "examined": int(out[1]), "mismatches": int(out[2])}
+
+
+DECIDE_EXITS = ("leaf_check", "pass_done", "another_pass", "exact")
+
+
+def selftest_decide_states(seed, n, device=-1):
+    """pt_selftest_decide_states: the n states of selftest_decide after the decision, by the host's
+    plain loop (device < 0) or by q_decide in a kernel on `device`.  Returns (states, exits,
+    slots): uint8 of shape (n, bytes per Query), the plain loop's count per exit (DECIDE_EXITS)
+    and per slot the states whose last examined slot it was."""
+    nb = C.c_uint32()
+    _check(_lib.pt_selftest_decide_states(device, seed, 0, None, 0, None, C.byref(nb)))
+    states = np.zeros((n, nb.value), np.uint8)
+    unset = np.uint64(0xffffffffffffffff)
+    counts = np.full(4 + 16, unset, np.uint64)   # (4 + PT_QHK are written; PT_QHK < 16)
+    _check(_lib.pt_selftest_decide_states(device, seed, n, _ptr(states), states.nbytes, _ptr(counts), C.byref(nb)))
+    exits = dict(zip(DECIDE_EXITS, (int(v) for v in counts[:4])))
+    return states, exits, [int(v) for v in counts[4:] if v != unset]
+
+
+def selftest_aux_words(scene):
+    """pt_selftest_aux_words: the query blob's aux entries against the host-form array.  Returns
+    {"entries", "empty", "leaf", "internal", "mismatches"}."""
+    out = np.zeros(5, np.uint64)
+    _check(_lib.pt_selftest_aux_words(scene._h, _ptr(out)))
+    return dict(zip(("entries", "empty", "leaf", "internal", "mismatches"), (int(v) for v in out)))
 
 
 def abi_version():
