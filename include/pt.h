@@ -666,6 +666,21 @@ int pt_selftest_features_host(pt_scene* s, uint64_t n, const float* xy, pt_featu
  * one thread.  in: opts->layout; out: w * h * 3 f32.  Needs no device and no scene. */
 int pt_selftest_filter_host(uint32_t w, uint32_t h, const pt_feature* features, const pt_filter_opts* opts,
                             const float* in, float* out);
+/* The parse as pt_scene_load left it, before pt_scene_prepare (afterwards: PT_E_INVALID, the
+ * primitives are reordered), every field as its raw bits.  out: an 80-byte header (width, height,
+ * samples, ray_depth u32; fov_x, background, camera position, right, up, forward f32), then per
+ * primitive in file order 100 bytes: u32 type; the three shape vectors; position; rotation x y z w;
+ * colour; emission; u32 material; f32 IOR.  warnings: the "unexpected command(...)" lines in order,
+ * each ended by '\n' (no NUL).  *need / *warn_need = the bytes either takes; out and warnings may be
+ * NULL to ask for them alone.  Needs no GPU. */
+int pt_selftest_scene_dump(const pt_scene* s, void* out, size_t cap, size_t* need, char* warnings, size_t warn_cap,
+                           size_t* warn_need);
+/* pt_scene_load_mem parsed in at most `stretches` (1 .. 64) stretches on as many threads, whatever
+ * the text's size and the machine's thread count (pt_scene_load_mem itself uses one stretch below
+ * 1 MiB, else up to 16).  cuts (may be NULL; room for cap) takes the offsets at which the stretches
+ * begin and end: 0, each cut, len; *n_cuts = their number (at most stretches + 1).  Needs no GPU. */
+int pt_selftest_scene_load_stretches(const char* text, size_t len, uint32_t stretches, pt_scene** out, uint64_t* cuts,
+                                     uint32_t cap, uint32_t* n_cuts);
 /* the 256-entry gamma threshold table used by the device tonemap */
 int pt_selftest_gamma_table(const pt_scene* s, float* thr256);
 /* session set-up without a device: the geometry (o's rank, world, window, traversal; o->device is

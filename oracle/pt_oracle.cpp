@@ -20,6 +20,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cfloat>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -364,6 +365,9 @@ struct LineStream {
         char* end = nullptr;
         const float f = std::strtof(tok.c_str(), &end);
         if (tok.empty() || end != tok.c_str() + tok.size()) { v = 0.f; fail = true; return; }
+        // overflow: libstdc++ (__convert_to_v) stores +-FLT_MAX and sets failbit; underflow does not fail
+        if (f == HUGE_VALF) { v = FLT_MAX; fail = true; return; }
+        if (f == -HUGE_VALF) { v = -FLT_MAX; fail = true; return; }
         v = f;
         if (pos >= s.size()) { /* eof reached: next read fails */ }
     }
@@ -458,7 +462,7 @@ std::string load_primitive(LineReader& in, Prim& prim) {
 }
 
 // src/sceneload.cpp:112-176
-void load_scene(Scene& S, const std::string& text) {
+void load_scene(Scene& S, const std::string& text, std::vector<std::string>* warnings = nullptr) {
     LineReader in(text);
     std::string line;
     while (in.next(line)) {
@@ -486,7 +490,10 @@ void load_scene(Scene& S, const std::string& text) {
             }
             case C_RAY_DEPTH: ss.get(S.ray_depth); break;
             case C_SAMPLES: ss.get(S.samples); break;
-            default: std::fprintf(stderr, "unexpected command(%s)\n", name.c_str()); break;
+            default:
+                std::fprintf(stderr, "unexpected command(%s)\n", name.c_str());
+                if (warnings) warnings->push_back("unexpected command(" + name + ")");
+                break;
         }
     }
 }
@@ -823,6 +830,35 @@ oracle_scene* oracle_load(const char* path) {
 }
 
 void oracle_free(oracle_scene* o) { delete o; }
+
+uint64_t oracle_parse_dump(const char* text, uint64_t len, void* out, uint64_t cap, char* warnings, uint64_t warn_cap,
+                           uint64_t* warn_need) {
+    Scene S;
+    std::vector<std::string> warn;
+    load_scene(S, std::string(text, (size_t)len), &warn);
+    const uint64_t need = 80 + 100 * (uint64_t)S.prims.size();
+    if (out && cap >= need) {
+        auto* b = static_cast<unsigned char*>(out);
+        auto put = [&b](const void* p, size_t n) { std::memcpy(b, p, n); b += n; };
+        const uint32_t u[4] = {S.W, S.H, S.samples, S.ray_depth};
+        put(u, 16); put(&S.fov_x, 4);
+        for (const V3* v : {&S.bg, &S.cam_pos, &S.cam_right, &S.cam_up, &S.cam_fwd}) { put(&v->x, 4); put(&v->y, 4); put(&v->z, 4); }
+        for (const Prim& p : S.prims) {
+            put(&p.type, 4);
+            for (const V3* v : {&p.a, &p.b, &p.c, &p.pos}) { put(&v->x, 4); put(&v->y, 4); put(&v->z, 4); }
+            put(&p.rot.x, 4); put(&p.rot.y, 4); put(&p.rot.z, 4); put(&p.rot.w, 4);
+            for (const V3* v : {&p.col, &p.emission}) { put(&v->x, 4); put(&v->y, 4); put(&v->z, 4); }
+            put(&p.mat, 4); put(&p.ior, 4);
+        }
+    }
+    uint64_t wn = 0;
+    for (const std::string& w : warn) {
+        if (warnings && wn + w.size() + 1 <= warn_cap) { std::memcpy(warnings + wn, w.data(), w.size()); warnings[wn + w.size()] = '\n'; }
+        wn += w.size() + 1;
+    }
+    if (warn_need) *warn_need = wn;
+    return need;
+}
 
 int oracle_info(const oracle_scene* o, uint32_t* out8) {
     const Scene& S = o->s;

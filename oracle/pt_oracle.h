@@ -10,6 +10,12 @@ extern "C" {
 typedef struct oracle_scene oracle_scene;
 oracle_scene* oracle_load(const char* path);
 void oracle_free(oracle_scene* o);
+/* load_scene alone on (text, len), no init_scene: the parse in ref_harness parse's layout (80-byte
+ * header + 100 bytes per primitive in file order).  Returns the bytes the dump takes; writes it
+ * where out has room for them (cap).  warnings (may be NULL) takes the "unexpected command(...)"
+ * lines, each ended by '\n', up to warn_cap bytes; *warn_need = their size. */
+uint64_t oracle_parse_dump(const char* text, uint64_t len, void* out, uint64_t cap, char* warnings, uint64_t warn_cap,
+                           uint64_t* warn_need);
 int oracle_info(const oracle_scene* o, uint32_t* out8);
 int oracle_dump_bvh(const oracle_scene* o, void* nodes_out, void* prims_out);
 int oracle_render(oracle_scene* o, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t spp,

@@ -29,6 +29,18 @@
 //   rays   <scene> <rays.f32> <out.bin>
 //          the caller's rays (n x 6 f32: origin, direction, used as they are) through the
 //          same two calls; the record per ray is trav's.
+//   parse  <scene> <out.bin>
+//          Scene::Load alone (src/sceneload.cpp:112-176; no InitScene, which aborts on
+//          plane-only and type-less scenes), every field as its raw bits.  Header (80 B):
+//          width, height, samples, ray_depth u32; fov_x, background, cam.pos, cam.right,
+//          cam.up, cam.forward f32.  Then per primitive in file order a 100-byte record:
+//          u32 type; dop_data, dop_data1, dop_data2 (the latter two zero unless TRIANGLE); pos; rotator as operator>> extracts
+//          it (x y z w); col; emission (f32 each); u32 material; f32 ior.  The reference
+//          gives several of these fields no initial value (Scene's and Camera's members,
+//          a Primitive's type, pos and dop_data*).  So that the dump is a function of the
+//          file alone, the Scene is built in zero-filled storage and the stack below the
+//          call is zero-filled first: such a field reads 0 unless a line wrote it.  The
+//          reference's "unexpected command(...)" lines go to stderr as they are.
 // Standard and glm headers first, so that only the reference's own classes
 // see the access override below.
 #include <algorithm>
@@ -96,6 +108,63 @@ static int mode_bvh(int argc, char** argv) {
         put_f32(op, tri ? p.dop_data2.x : 0.f); put_f32(op, tri ? p.dop_data2.y : 0.f); put_f32(op, tri ? p.dop_data2.z : 0.f);
         put_f32(op, p.pos.x); put_f32(op, p.pos.y); put_f32(op, p.pos.z);
     }
+    return 0;
+}
+
+// zero the stack that Scene::Load's frames will occupy (through a volatile pointer, so
+// that the stores stay).  What a field without an initial value then reads is still the
+// compiler's choice of stack slots: the fixtures regenerate byte-identically with the
+// compiler and flags of oracle/build_ref.sh, and tests/_loader_cases.py keeps its cases to
+// fields that a line of the file wrote, or that read this zero with that build.
+__attribute__((noinline)) static void zero_stack_below() {
+    volatile unsigned char pad[1 << 16];
+    for (size_t i = 0; i < sizeof(pad); ++i) pad[i] = 0;
+}
+
+static void put_v3(std::ofstream& o, const glm::vec3& v) { put_f32(o, v.x); put_f32(o, v.y); put_f32(o, v.z); }
+
+static int mode_parse(int argc, char** argv) {
+    if (argc < 4) return 2;
+    std::ifstream in(argv[2], std::ios::binary);
+    if (!in) { std::fprintf(stderr, "cannot open %s\n", argv[2]); return 1; }
+    // zero-filled storage, written through a volatile pointer: the constructor's own
+    // stores are then the only other ones the fields see before Load
+    void* mem = std::aligned_alloc(alignof(Scene) < 64 ? 64 : alignof(Scene), (sizeof(Scene) + 63) / 64 * 64);
+    if (!mem) return 1;
+    {
+        volatile unsigned char* b = static_cast<volatile unsigned char*>(mem);
+        for (size_t i = 0; i < sizeof(Scene); ++i) b[i] = 0;
+    }
+    Scene* sp = new (mem) Scene;
+    Scene& s = *sp;
+    zero_stack_below();
+    s.Load(in);
+    std::ofstream o(argv[3], std::ios::binary);
+    put_u32(o, s.cam.width); put_u32(o, s.cam.height); put_u32(o, s.samples); put_u32(o, s.ray_depth);
+    put_f32(o, s.cam.fov_x);
+    put_v3(o, s.background.rgb); put_v3(o, s.cam.pos); put_v3(o, s.cam.right); put_v3(o, s.cam.up);
+    put_v3(o, s.cam.forward);
+    for (const Primitive& p : s.primitives) {
+        uint32_t type, mat;
+        static_assert(sizeof(p.primitive_type) == 4 && sizeof(p.material) == 4, "enum width");
+        std::memcpy(&type, &p.primitive_type, 4);
+        std::memcpy(&mat, &p.material, 4);
+        put_u32(o, type);
+        // (dop_data1 and dop_data2 of anything but a TRIANGLE are never written by the reference and
+        // lie in a temporary whose stack slots hold other objects before it: 0, as mode bvh dumps them)
+        const bool tri = p.primitive_type == PRIMITIVE_TYPE::TRIANGLE;
+        const glm::vec3 zero{0.f, 0.f, 0.f};
+        put_v3(o, p.dop_data); put_v3(o, tri ? p.dop_data1 : zero); put_v3(o, tri ? p.dop_data2 : zero);
+        put_v3(o, p.pos);
+        put_f32(o, p.rotator.x); put_f32(o, p.rotator.y); put_f32(o, p.rotator.z); put_f32(o, p.rotator.w);
+        put_v3(o, p.col.rgb); put_v3(o, p.emission.rgb);
+        put_u32(o, mat);
+        put_f32(o, p.ior);
+    }
+    o.close();
+    if (!o) { std::fprintf(stderr, "cannot write %s\n", argv[3]); return 1; }
+    sp->~Scene();
+    std::free(mem);
     return 0;
 }
 
@@ -241,7 +310,7 @@ static int mode_rays(int argc, char** argv) {
 }
 
 int main(int argc, char** argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: ref_harness bvh|render|rng|trav|rays ...\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: ref_harness bvh|parse|render|rng|trav|rays ...\n"); return 2; }
     const std::string m = argv[1];
     int rc = 2;
     if (m == "bvh") rc = mode_bvh(argc, argv);
@@ -249,6 +318,7 @@ int main(int argc, char** argv) {
     else if (m == "rng") rc = mode_rng(argc, argv);
     else if (m == "trav") rc = mode_trav(argc, argv);
     else if (m == "rays") rc = mode_rays(argc, argv);
+    else if (m == "parse") rc = mode_parse(argc, argv);
     if (rc == 2) std::fprintf(stderr, "bad arguments for mode %s\n", m.c_str());
     return rc;
 }

@@ -41,6 +41,10 @@ struct HScene {
 
 // Parse the hw5 grammar (scene_load.cpp).  Throws std::runtime_error on I/O failure only.
 void parse_scene(const char* text, size_t len, HScene& S);
+// ... in at most T stretches, whatever the file's size and the machine's threads (parse_scene
+// picks T); and the offsets at which the stretches begin and end: 0, the cuts, len
+void parse_scene_stretches(const char* text, size_t len, HScene& S, unsigned T);
+std::vector<size_t> scene_stretch_cuts(const char* text, size_t len, unsigned T);
 
 // Faithful reference BVH (bvh_build.cpp): reorders prims[0, n) like
 // BVH_t::InitTree and appends nodes in preorder.

@@ -9,12 +9,16 @@
 //    first non-primitive command; that command is then re-dispatched against
 //    the *stale* NEW_PRIMITIVE line's stream (sceneload.cpp:120-159), so its
 //    arguments are not read (values stay as they were);
-//  * a failed numeric extraction stores 0 and poisons the rest of the line;
+//  * a failed numeric extraction stores 0 and poisons the rest of the line; a float token
+//    that overflows stores +-FLT_MAX and poisons it too (one that underflows is read);
+//    a token may be as long as its line;
 //    reading past the end of a line leaves the value unchanged;
 //  * a primitive-type line (PLANE/BOX/ELLIPSOID/TRIANGLE) resets the whole
 //    primitive (`primitive = Primitive(...)`, sceneload.cpp:49-72);
 //  * unknown top-level commands warn on stderr (sceneload.cpp:170-172).
 #include <ctype.h>
+#include <float.h>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -113,13 +117,19 @@ struct Cursor {
         p = q;
         const size_t n = (size_t)(q - b);
         if (dig && fast_float(b, q, v)) return;
+        // the token is bounded by the line: on the stack where it fits, else a heap copy
         char buf[128];
-        if (n == 0 || n >= sizeof(buf)) { v = 0.f; fail = true; return; }
-        memcpy(buf, b, n);
-        buf[n] = '\0';
+        std::string big;
+        const char* z = buf;
+        if (n == 0) { v = 0.f; fail = true; return; }
+        if (n < sizeof(buf)) { memcpy(buf, b, n); buf[n] = '\0'; }
+        else { big.assign(b, n); z = big.c_str(); }
         char* end = nullptr;
-        const float f = strtof(buf, &end);
-        if (end != buf + n) { v = 0.f; fail = true; return; }
+        const float f = strtof(z, &end);
+        if (end != z + n) { v = 0.f; fail = true; return; }
+        // overflow: +-FLT_MAX and failbit (libstdc++ __convert_to_v); underflow does not fail
+        if (f == HUGE_VALF) { v = FLT_MAX; fail = true; return; }
+        if (f == -HUGE_VALF) { v = -FLT_MAX; fail = true; return; }
         v = f;
     }
     // operator>>(unsigned&)
@@ -291,9 +301,7 @@ bool starts_new_primitive(const char* p, const char* e) {
 // it, and the top level dispatches it; NEW_PRIMITIVE reads nothing from the stale
 // stream) -- so stretches that begin at such lines parse independently.  Their
 // primitives are concatenated in order, and their top-level commands replayed in order.
-void parse_scene(const char* text, size_t len, HScene& S) {
-    unsigned T = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    if (len < (1u << 20)) T = 1;
+std::vector<size_t> scene_stretch_cuts(const char* text, size_t len, unsigned T) {
     std::vector<size_t> cut{0};
     for (unsigned k = 1; k < T; ++k) {
         size_t at = std::max(cut.back(), len * k / T);
@@ -310,6 +318,17 @@ void parse_scene(const char* text, size_t len, HScene& S) {
         if (at > cut.back()) cut.push_back(at);
     }
     cut.push_back(len);
+    return cut;
+}
+
+void parse_scene(const char* text, size_t len, HScene& S) {
+    unsigned T = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+    if (len < (1u << 20)) T = 1;
+    parse_scene_stretches(text, len, S, T);
+}
+
+void parse_scene_stretches(const char* text, size_t len, HScene& S, unsigned T) {
+    const std::vector<size_t> cut = scene_stretch_cuts(text, len, std::max(1u, T));
     const size_t n = cut.size() - 1;
     std::vector<Stretch> parts(n);
     if (n == 1) {

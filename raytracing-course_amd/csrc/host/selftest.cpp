@@ -509,6 +509,61 @@ int pt_selftest_gamma_table(const pt_scene* s, float* thr256) {
     return PT_OK;
 }
 
+// pt_scene_load_mem in at most `stretches` stretches, and where they begin and end
+int pt_selftest_scene_load_stretches(const char* text, size_t len, uint32_t stretches, pt_scene** out, uint64_t* cuts,
+                                     uint32_t cap, uint32_t* n_cuts) {
+    if (!out || !n_cuts || (!text && len) || stretches == 0 || stretches > 64) return fail(PT_E_INVALID, "bad argument");
+    const std::vector<size_t> cut = pth::scene_stretch_cuts(text, len, stretches);
+    *n_cuts = (uint32_t)cut.size();
+    if (cuts) {
+        if (cap < cut.size()) return fail(PT_E_INVALID, "cuts buffer too small");
+        for (size_t i = 0; i < cut.size(); ++i) cuts[i] = cut[i];
+    }
+    auto* s = new pt_scene();
+    try {
+        pth::parse_scene_stretches(text, len, s->hs, stretches);
+    } catch (const std::exception& e) {
+        delete s;
+        return fail(PT_E_SCENE, e.what());
+    }
+    *out = s;
+    return PT_OK;
+}
+
+// the parse as Scene::Load leaves it (before pt_scene_prepare reorders the primitives)
+int pt_selftest_scene_dump(const pt_scene* s, void* out, size_t cap, size_t* need, char* warnings, size_t warn_cap,
+                           size_t* warn_need) {
+    if (!s || !need || !warn_need) return fail(PT_E_INVALID, "null argument");
+    if (s->prepared) return fail(PT_E_INVALID, "scene already prepared: its primitives are no longer in load order");
+    const pth::HScene& h = s->hs;
+    *need = 80 + 100 * h.prims.size();
+    *warn_need = 0;
+    for (const std::string& w : h.warnings) *warn_need += w.size() + 1;
+    if (out) {
+        if (cap < *need) return fail(PT_E_INVALID, "dump buffer too small");
+        auto* b = static_cast<unsigned char*>(out);
+        const uint32_t u[4] = {h.W, h.H, h.samples, h.depth};
+        memcpy(b, u, 16); memcpy(b + 16, &h.fov_x, 4); memcpy(b + 20, h.bg, 12); memcpy(b + 32, h.cam_pos, 12);
+        memcpy(b + 44, h.cam_right, 12); memcpy(b + 56, h.cam_up, 12); memcpy(b + 68, h.cam_fwd, 12);
+        b += 80;
+        for (const pth::HPrim& p : h.prims) {
+            memcpy(b, &p.type, 4); memcpy(b + 4, p.a, 12); memcpy(b + 16, p.b, 12); memcpy(b + 28, p.c, 12);
+            memcpy(b + 40, p.pos, 12); memcpy(b + 52, p.rot, 16); memcpy(b + 68, p.col, 12);
+            memcpy(b + 80, p.emis, 12); memcpy(b + 92, &p.mat, 4); memcpy(b + 96, &p.ior, 4);
+            b += 100;
+        }
+    }
+    if (warnings) {
+        if (warn_cap < *warn_need) return fail(PT_E_INVALID, "warnings buffer too small");
+        for (const std::string& w : h.warnings) {
+            memcpy(warnings, w.data(), w.size());
+            warnings[w.size()] = '\n';
+            warnings += w.size() + 1;
+        }
+    }
+    return PT_OK;
+}
+
 static_assert(pt::MATH_LOGF == PT_MATH_LOGF && pt::MATH_RNG == PT_MATH_RNG && pt::MATH_NORMAL3 == PT_MATH_NORMAL3 &&
                   pt::MATH_COSINE == PT_MATH_COSINE && pt::MATH_FRESNEL == PT_MATH_FRESNEL &&
                   pt::MATH_RESOLVE == PT_MATH_RESOLVE && pt::MATH_ARITH == PT_MATH_ARITH && pt::MATH_N == 7u,

@@ -238,6 +238,10 @@ _sig = {
     "pt_selftest_features_host": (C.c_int, [_P, C.c_uint64, _P, _P, _P]),
     "pt_selftest_filter_host": (C.c_int, [C.c_uint32, C.c_uint32, _P, C.POINTER(FilterOpts), _P, _P]),
     "pt_selftest_gamma_table": (C.c_int, [_P, _P]),
+    "pt_selftest_scene_load_stretches": (C.c_int, [C.c_char_p, C.c_size_t, C.c_uint32, C.POINTER(_P), _P, C.c_uint32,
+                                                   C.POINTER(C.c_uint32)]),
+    "pt_selftest_scene_dump": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P, C.c_size_t,
+                                         C.POINTER(C.c_size_t)]),
     "pt_selftest_wave_plan": (C.c_int, [_P, C.POINTER(SessionOpts), C.c_uint32, C.c_char_p, C.c_size_t]),
     "pt_selftest_fold_shape": (C.c_int, [C.c_uint32] * 4 + [C.POINTER(C.c_uint32)] * 2),
     "pt_selftest_fit_block": (C.c_int, [C.c_uint32] * 2 + [C.POINTER(C.c_uint32)] * 3),
@@ -303,6 +307,16 @@ class Scene:
         _check(_lib.pt_scene_load_mem(b, len(b), C.byref(h)))
         return cls(h)
 
+    @classmethod
+    def selftest_loads_stretches(cls, text, stretches):
+        """pt_selftest_scene_load_stretches: (scene, [0, cuts..., len]) of `text` parsed in at most
+        `stretches` stretches."""
+        b = text.encode() if isinstance(text, str) else bytes(text)
+        h, n = _P(), C.c_uint32(0)
+        cuts = np.zeros(stretches + 1, np.uint64)
+        _check(_lib.pt_selftest_scene_load_stretches(b, len(b), stretches, C.byref(h), _ptr(cuts), len(cuts), C.byref(n)))
+        return cls(h), [int(c) for c in cuts[:n.value]]
+
     def close(self):
         if getattr(self, "_h", None) and _lib is not None:
             _lib.pt_scene_free(self._h)
@@ -337,6 +351,16 @@ class Scene:
         pb = np.zeros(inf["n_prims"] * 52, np.uint8)
         _check(_lib.pt_scene_dump_bvh(self._h, _ptr(nb), nb.nbytes, _ptr(pb), pb.nbytes))
         return nb.tobytes(), pb.tobytes()
+
+    def selftest_scene_dump(self):
+        """pt_selftest_scene_dump: (dump bytes, warning lines) of the parse, before prepare()."""
+        need, wneed = C.c_size_t(0), C.c_size_t(0)
+        _check(_lib.pt_selftest_scene_dump(self._h, None, 0, C.byref(need), None, 0, C.byref(wneed)))
+        out = np.zeros(need.value, np.uint8)
+        warn = np.zeros(max(1, wneed.value), np.uint8)
+        _check(_lib.pt_selftest_scene_dump(self._h, _ptr(out), out.nbytes, C.byref(need), _ptr(warn), wneed.value,
+                                           C.byref(wneed)))
+        return out.tobytes(), warn[:wneed.value].tobytes().decode("latin-1").split("\n")[:-1]
 
     def render(self, device=0, ngpu=1, samples=0, spp_per_launch=0, radiance=False, progress=False, window=None,
                traversal=TRAVERSAL_REPLAY, gather=GATHER_AUTO, check=True):

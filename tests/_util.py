@@ -46,6 +46,8 @@ def oracle():
         lib.oracle_load.argtypes = [C.c_char_p]
         lib.oracle_free.argtypes = [P]
         lib.oracle_info.argtypes = [P, P]
+        lib.oracle_parse_dump.restype = C.c_uint64
+        lib.oracle_parse_dump.argtypes = [C.c_char_p, C.c_uint64, P, C.c_uint64, P, C.c_uint64, C.POINTER(C.c_uint64)]
         lib.oracle_dump_bvh.argtypes = [P, P, P]
         lib.oracle_render.argtypes = [P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, P, P, P]
         lib.oracle_render_census.argtypes = lib.oracle_render.argtypes + [P]
@@ -98,6 +100,19 @@ class OracleScene:
         if getattr(self, "h", None):
             self.lib.oracle_free(self.h)
             self.h = None
+
+    @staticmethod
+    def parse_dump(text):
+        """(dump bytes, warning lines) of the restatement's parse of `text` alone (no init_scene), in
+        the layout of ref_harness parse and of ptrace's Scene.selftest_scene_dump"""
+        lib = oracle()
+        text = bytes(text)
+        wn = C.c_uint64(0)
+        need = lib.oracle_parse_dump(text, len(text), None, 0, None, 0, C.byref(wn))
+        out = np.zeros(need, np.uint8)
+        warn = np.zeros(max(1, wn.value), np.uint8)
+        assert lib.oracle_parse_dump(text, len(text), _p(out), need, _p(warn), wn.value, C.byref(wn)) == need
+        return out.tobytes(), warn[:wn.value].tobytes().decode("latin-1").split("\n")[:-1]
 
     def render(self, x0=0, y0=0, w=None, h=None, spp=0, threads=0, census=False):
         """(image, radiance, counters); with census=True the counters also hold "census": the
