@@ -8,7 +8,10 @@
 //   session.cpp   tile sessions: set-up (geometry, arena), the megakernel pass, resolve, stats (pt_session_*)
 //   wave_plan.cpp the wavefront pass's launch shapes and capacities (plan_wave: no device needed)
 //   rounds.cpp    the wavefront pass: path rounds, early / final cooperative launches
-//   render.cpp    Scene::Render equivalent: per-GPU threads, the RCCL / host gather, PPM
+//   render.cpp    Scene::Render equivalent, pt_render as its phases: the options resolved, the refusals, the
+//                 pinned staging buffer, the ranks (a host thread and a session per GPU: set up, wait for
+//                 its turn, render, resolve), their errors, the gather (RCCL / one session / host), the
+//                 PT_STATS reports, the radiance read-back and the merged stats; PPM
 //   qctx.cpp      what the batch contexts below share: set-up, launch shape, statistics, the event timer and
 //                 (here, as templates) their creation and the one-shot host forms' chunk loop
 //   rayq.cpp      the ray-query engine: closest-hit queries for the caller's rays (pt_rayq_*, pt_intersect)
@@ -28,7 +31,8 @@
 //                 samples_range), and the slot -> record map on the host (pt_selftest_count_records)
 //   noise.cpp     a session's own noise estimate and the adaptive step planned from it (pt_session_mark /
 //                 noise / plan / refine), and the plan on the host (pt_selftest_refine_plan)
-//   selftest.cpp  host execution of the device query / integrator code, and pt_selftest_math (the
+//   selftest.cpp  host execution of the device query / integrator code (one HostQuery, the twin of
+//                 pt_batch.h's start_query and QStats, under every hook), and pt_selftest_math (the
 //                 device code's scalar functions on the host or in k_selftest_math) (tests only; one
 //                 hook, pt_selftest_wave_plan, is in session.cpp beside the set-up it reports, another,
 //                 pt_selftest_fold_shape, in qctx.cpp)
@@ -200,6 +204,8 @@ pt::SceneView device_view(const pt_scene* s, const DevScene& ds);   // ... of an
 int handoff_site(const char* name);
 // the summed counter block's slots CTR_RAYS .. CTR_FALLBACKS_RAY as pt_stats' rays .. fallbacks_ray
 void counter_stats(const unsigned long long* c, pt_stats* st);
+// a rank's pt_session_stats into a render's: every field by its rule (session.cpp, beside pt_session_stats)
+void merge_stats(pt_stats& into, const pt_stats& rank);
 
 // The wavefront pass's launch shapes and capacities (wave_plan.cpp): fixed at session creation,
 // a function of the scene's tree facts, the CU count, the owned pixels and PT_TUNE.  (Run state

@@ -27,6 +27,74 @@ struct HostVStore {
         idm = v[3 * k]; s1 = pt::u2f(v[3 * k + 1]); s2 = pt::u2f(v[3 * k + 2]);
     }
 };
+// The host twin of start_query and QStats (pt_batch.h): a closest-hit query run to completion on
+// this thread's stack, and what the device counts of it -- the query's QCounts added to `C` (the
+// guard bit masked out of `planes`), the guard itself (C.errs), the queries that took the exact DFS
+// and, of those, the non-finite rays.  trace_path_with counts a path's rays and calls the object;
+// a hook that runs single queries calls query().
+enum QEngine { QE_RUN, QE_COOP, QE_TRIP };   // q_run | qc_query (pt_coop.h) | q_run_trip, the path engine's trips
+struct HostQuery {
+    const pt::SceneView& V;
+    const QEngine engine;
+    const uint32_t aux_extra;       // QE_TRIP: extra aux-node steps per trip
+    const bool count_nonfinite;     // false: exact_ray stays 0 (a hook whose engine has no such counter)
+    const bool log;                 // PT_TUNE qstats: a record per query in qlog
+    HostStack stk;
+    pt::Counts C{};
+    uint64_t exact_ray = 0;
+    uint64_t diag[3] = {0, 0, 0};   // PT_QDIAG: queries, aux steps, range-test steps
+    std::vector<std::array<uint32_t, 4>> qlog;
+    explicit HostQuery(const pt::SceneView& v, QEngine e = QE_RUN, uint32_t extra = 1u, bool nonfinite = true,
+                       bool qstats = false)
+        : V(v), engine(e), aux_extra(extra), count_nonfinite(nonfinite), log(qstats) {}
+
+    int operator()(const pt::Ray& r, pt::Hit& h, pt::Counts& cc) {
+        pt::QCounts Q{};
+        uint32_t ex = 0;
+        const int id = engine == QE_COOP   ? pt::qc_query(V, r, stk, h, Q, ex)
+                       : engine == QE_TRIP ? pt::q_run_trip(V, r, stk, h, Q, ex, aux_extra)
+                                           : pt::q_run(V, r, stk, h, Q, ex);
+        if (Q.planes & 0x80000000u) cc.errs |= 4u;   // recomputed hit differs (verdict())
+        cc.nodes += Q.nodes; cc.ptests += Q.ptests; cc.planes += Q.planes & 0x7fffffffu; cc.aux += Q.aux;
+        cc.fallbacks += ex;
+        const float w = count_nonfinite ? pt::q_prep(V, r).w : 0.f;
+        if (w != w) exact_ray++;   // a non-finite ray (q_init_pre: Q_EXACT from the start)
+#ifdef PT_QDIAG
+        diag[0]++; diag[1] += Q.aux; diag[2] += Q.aux_ranges;
+        if (log) qlog.push_back({Q.aux, Q.rc_acc | (Q.rc_rej << 16), Q.rc_walk, Q.cands | (Q.passes << 16)});
+#else
+        if (log) qlog.push_back({Q.aux, Q.nodes, Q.ptests | (ex << 31), 0u});
+#endif
+        return id;
+    }
+    int query(const pt::Ray& r, pt::Hit& h) { C.rays++; return (*this)(r, h, C); }
+    // the guard's "must never happen"
+    int verdict() const { return C.errs ? fail(PT_E_INVALID, "recomputed closest hit differs from the query's") : PT_OK; }
+    // counters8 (null: none asked for): the slots CTR_RAYS .. CTR_FALLBACKS_RAY, as QStats::flush fills them
+    void pack(uint64_t* counters8) const {
+        if (!counters8) return;
+        uint64_t c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        c[pt::CTR_RAYS] = C.rays; c[pt::CTR_NODES] = C.nodes; c[pt::CTR_PTESTS] = C.ptests; c[pt::CTR_PLANES] = C.planes;
+        c[pt::CTR_ERRORS] = C.errs; c[pt::CTR_AUX] = C.aux; c[pt::CTR_FALLBACKS] = C.fallbacks;
+        c[pt::CTR_FALLBACKS_RAY] = exact_ray;
+        memcpy(counters8, c, sizeof(c));
+    }
+    // make DEFS=-DPT_QDIAG: the line of n threads' queries
+    static void qdiag(const HostQuery* q, size_t n) {
+#ifdef PT_QDIAG
+        uint64_t a[3] = {0, 0, 0};
+        for (size_t i = 0; i < n; ++i)
+            for (int k = 0; k < 3; ++k) a[k] += q[i].diag[k];
+        fprintf(stderr, "qdiag: %llu rays, %llu aux steps, %llu of a lane that needs the range test\n",
+                (unsigned long long)a[0], (unsigned long long)a[1], (unsigned long long)a[2]);
+#endif
+    }
+};
+// PT_TUNE qengine=coop (and, where the hook has it, =trip) as the query's engine
+QEngine tuned_engine(bool with_trip) {
+    const std::string e = tune_str("qengine");
+    return e == "coop" ? QE_COOP : with_trip && e == "trip" ? QE_TRIP : QE_RUN;
+}
 // the general body of q_exec_aux on this thread for the holder's life (pt_query.h)
 struct ForceGeneral {
     const bool was;
@@ -112,40 +180,25 @@ int pt_selftest_ray_intersection(pt_scene* s, int32_t traversal, uint32_t n, con
     if (rc) return rc;
     const pt::SceneView V = host_view(s, traversal);
     const pt::ReplayCfg cfg = replay_cfg(s);
-    HostStack stk;
-    pt::Counts C{};
-    const bool coop = tune_str("qengine") == "coop";   // the cooperative engine's query (pt_coop.h)
+    // qengine=coop | mega | trip (the trips with PT_TUNE aux_extra extra aux-node steps each); the
+    // non-finite rays are not counted here (CTR_FALLBACKS_RAY stays 0)
     const bool mega = tune_str("qengine") == "mega";   // the megakernel's FAST query (k_trace<true>)
-    // the state machine in the path engine's trips (q_trip), PT_TUNE aux_extra extra aux-node steps each
-    const bool trip = tune_str("qengine") == "trip";
-    const uint32_t aux_extra = (uint32_t)std::max(0, tune_int("aux_extra", 1));
+    HostQuery q(V, tuned_engine(true), (uint32_t)std::max(0, tune_int("aux_extra", 1)), false);
     // qforms=general: the general q_exec_aux body on every step of this call
     const ForceGeneral forced(tune_str("qforms") == "general");
-#ifdef PT_QDIAG
-    uint64_t aux_steps = 0, aux_ranges = 0;
-#endif
     for (uint32_t i = 0; i < n; ++i) {
         pt::Ray r;
         r.o = pt::mk3(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]);
         r.d = pt::mk3(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
         pt::Hit h;
         int id;
-        if (traversal == PT_TRAVERSAL_REPLAY && mega) {
-            id = pt::ray_intersection<true>(V, cfg, r, stk, h, C);
-        } else if (traversal == PT_TRAVERSAL_REPLAY) {
-            pt::QCounts Q{0u, 0u, 0u, 0u};
-            uint32_t ex = 0;
-            id = coop   ? pt::qc_query(V, r, stk, h, Q, ex)
-                 : trip ? pt::q_run_trip(V, r, stk, h, Q, ex, aux_extra)
-                        : pt::q_run(V, r, stk, h, Q, ex);
-            if (Q.planes & 0x80000000u) return fail(PT_E_INVALID, "recomputed closest hit differs from the query's");
-            C.rays++;
-            C.nodes += Q.nodes; C.ptests += Q.ptests; C.planes += Q.planes; C.aux += Q.aux; C.fallbacks += ex;
-#ifdef PT_QDIAG
-            aux_steps += Q.aux; aux_ranges += Q.aux_ranges;
-#endif
+        if (traversal != PT_TRAVERSAL_REPLAY) {
+            id = pt::ray_intersection<false>(V, cfg, r, q.stk, h, q.C);
+        } else if (mega) {
+            id = pt::ray_intersection<true>(V, cfg, r, q.stk, h, q.C);
         } else {
-            id = pt::ray_intersection<false>(V, cfg, r, stk, h, C);
+            id = q.query(r, h);
+            if ((rc = q.verdict())) return rc;
         }
         ids[i] = id;
         const bool ok = id != -1;
@@ -155,18 +208,10 @@ int pt_selftest_ray_intersection(pt_scene* s, int32_t traversal, uint32_t n, con
         hits[5 * i + 3] = ok ? h.n.z : 0.f;
         hits[5 * i + 4] = ok ? (h.interior ? 1.f : 0.f) : 0.f;
     }
-#ifdef PT_QDIAG
-    fprintf(stderr, "qdiag: %u rays, %llu aux steps, %llu of a lane that needs the range test\n", n,
-            (unsigned long long)aux_steps, (unsigned long long)aux_ranges);
-#endif
-    if (counters8) {
-        uint64_t c[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // (slots CTR_RAYS .. CTR_FALLBACKS_RAY)
-        c[pt::CTR_RAYS] = C.rays; c[pt::CTR_NODES] = C.nodes; c[pt::CTR_PTESTS] = C.ptests; c[pt::CTR_PLANES] = C.planes;
-        c[pt::CTR_ERRORS] = C.errs; c[pt::CTR_AUX] = C.aux; c[pt::CTR_FALLBACKS] = C.fallbacks;
-        memcpy(counters8, c, sizeof(c));
-    }
+    HostQuery::qdiag(&q, 1);
+    q.pack(counters8);
     // the exact DFS alone on this stack: it must have stayed within the words the device forms give it
-    if (traversal == PT_TRAVERSAL_EXACT && stk.v.size() > std::max<uint32_t>(s->max_stack, 1u))
+    if (traversal == PT_TRAVERSAL_EXACT && q.stk.v.size() > std::max<uint32_t>(s->max_stack, 1u))
         return fail(PT_E_INVALID, "the exact DFS used more stack words than max_stack");
     return PT_OK;
 }
@@ -268,23 +313,16 @@ int pt_selftest_render_host(pt_scene* s, int32_t traversal, uint32_t x0, uint32_
     const pt::CamView cam = make_cam(s);
     const uint32_t S = spp ? spp : s->hs.samples;
     const uint32_t nt = std::max(1u, std::thread::hardware_concurrency());
-    std::vector<std::thread> th;
-    std::vector<uint32_t> errs(nt, 0);
     // diagnostics: PT_TUNE qstats=<file> dumps per-query {aux visits, node tests, prim tests, exact} (u32 x4)
-    const std::string qpaths = tune_str("qstats");
-    const char* qpath = qpaths.empty() ? nullptr : qpaths.c_str();
-    std::vector<std::vector<std::array<uint32_t, 4>>> qlogs(nt);
-#ifdef PT_QDIAG
-    std::vector<std::array<uint64_t, 3>> qd(nt, {0, 0, 0});   // per thread: queries, aux steps, range-test steps
-#endif
-    const bool coop = tune_str("qengine") == "coop";   // the cooperative engine's query (pt_coop.h)
+    const std::string qpath = tune_str("qstats");
     const bool mega = tune_str("qengine") == "mega";   // the megakernel's FAST query (k_trace<true>)
+    // a thread's query: the wavefront engine's (pt_query.h state machine) or qengine=coop's, run to completion
+    std::vector<HostQuery> qs(nt, HostQuery(V, tuned_engine(false), 1u, false, !qpath.empty()));
+    std::vector<std::thread> th;
     for (uint32_t t = 0; t < nt; ++t) {
         th.emplace_back([&, t]() {
-            std::vector<std::array<uint32_t, 4>>* qlog = qpath ? &qlogs[t] : nullptr;
-            HostStack stk;
+            HostQuery& q = qs[t];
             HostVStore vs;
-            pt::Counts C{};
             for (uint64_t k = t; k < (uint64_t)w * h; k += nt) {
                 const uint32_t x = x0 + (uint32_t)(k % w), y = y0 + (uint32_t)(k / w);
                 pt::Rng R = pt::rng_seed(y * s->hs.W + x);
@@ -293,52 +331,28 @@ int pt_selftest_render_host(pt_scene* s, int32_t traversal, uint32_t x0, uint32_
                     const float fx = (float)x + pt::rng_uniform(R);
                     const float fy = (float)y + pt::rng_uniform(R);
                     const pt::Ray ray = pt::camera_ray(cam, fx, fy);
-                    if (traversal == PT_TRAVERSAL_REPLAY && mega) {
-                        sum = sum + pt::trace_path<true>(V, cfg, ray, s->hs.depth, R, stk, vs, C);
-                    } else if (traversal == PT_TRAVERSAL_REPLAY) {
-                        // the wavefront engine's query (pt_query.h state machine), run to completion
-                        auto q = [&](const pt::Ray& rr, pt::Hit& hh, pt::Counts& cc) {
-                            pt::QCounts Q{};
-                            uint32_t ex = 0;
-                            const int id = coop ? pt::qc_query(V, rr, stk, hh, Q, ex) : pt::q_run(V, rr, stk, hh, Q, ex);
-                            cc.fallbacks += ex;
-                            if (Q.planes & 0x80000000u) cc.errs |= 4u;   // recomputed hit differs (checked below)
-#ifdef PT_QDIAG
-                            qd[t][0]++; qd[t][1] += Q.aux; qd[t][2] += Q.aux_ranges;
-                            if (qlog) qlog->push_back({Q.aux, Q.rc_acc | (Q.rc_rej << 16), Q.rc_walk, Q.cands | (Q.passes << 16)});
-#else
-                            if (qlog) qlog->push_back({Q.aux, Q.nodes, Q.ptests | (ex << 31), 0u});
-#endif
-                            return id;
-                        };
-                        sum = sum + pt::trace_path_with(V, q, ray, s->hs.depth, R, vs, C);
-                    } else {
-                        sum = sum + pt::trace_path<false>(V, cfg, ray, s->hs.depth, R, stk, vs, C);
-                    }
+                    if (traversal != PT_TRAVERSAL_REPLAY)
+                        sum = sum + pt::trace_path<false>(V, cfg, ray, s->hs.depth, R, q.stk, vs, q.C);
+                    else if (mega)
+                        sum = sum + pt::trace_path<true>(V, cfg, ray, s->hs.depth, R, q.stk, vs, q.C);
+                    else
+                        sum = sum + pt::trace_path_with(V, q, ray, s->hs.depth, R, vs, q.C);
                 }
                 radiance[3 * k] = pt::sample_mean(sum.x, S);
                 radiance[3 * k + 1] = pt::sample_mean(sum.y, S);
                 radiance[3 * k + 2] = pt::sample_mean(sum.z, S);
             }
-            errs[t] = C.errs;
         });
     }
     for (auto& x : th) x.join();
-#ifdef PT_QDIAG
-    {
-        uint64_t a[3] = {0, 0, 0};
-        for (auto& v : qd) for (int k = 0; k < 3; ++k) a[k] += v[k];
-        fprintf(stderr, "qdiag: %llu rays, %llu aux steps, %llu of a lane that needs the range test\n",
-                (unsigned long long)a[0], (unsigned long long)a[1], (unsigned long long)a[2]);
-    }
-#endif
-    if (qpath)
-        if (FILE* f = fopen(qpath, "wb")) {
-            for (auto& v : qlogs) fwrite(v.data(), 16, v.size(), f);
+    HostQuery::qdiag(qs.data(), qs.size());
+    if (!qpath.empty())
+        if (FILE* f = fopen(qpath.c_str(), "wb")) {
+            for (const HostQuery& q : qs) fwrite(q.qlog.data(), 16, q.qlog.size(), f);
             fclose(f);
         }
-    for (uint32_t e : errs)
-        if (e) return fail(PT_E_INVALID, "recomputed closest hit differs from the query's");
+    for (const HostQuery& q : qs)
+        if ((rc = q.verdict())) return rc;
     return PT_OK;
 }
 
@@ -348,39 +362,19 @@ int pt_selftest_paths_host(pt_scene* s, uint64_t n, const pt_path_ray* in, pt_pa
     int rc = pt_scene_prepare(s);
     if (rc) return rc;
     const pt::SceneView V = host_view(s, PT_TRAVERSAL_REPLAY);
-    HostStack stk;
+    HostQuery q(V);   // the batch radiance engine's query
     HostVStore vs;
-    pt::Counts C{};
-    uint64_t exact_ray = 0;
     for (uint64_t i = 0; i < n; ++i) {
-        // the batch radiance engine's query (pt_query.h state machine), run to completion
-        auto q = [&](const pt::Ray& rr, pt::Hit& hh, pt::Counts& cc) {
-            pt::QCounts Q{};
-            uint32_t ex = 0;
-            const int id = pt::q_run(V, rr, stk, hh, Q, ex);
-            cc.fallbacks += ex;
-            const float w = pt::q_prep(V, rr).w;
-            if (w != w) exact_ray++;   // a non-finite ray (q_init_pre: Q_EXACT from the start)
-            if (Q.planes & 0x80000000u) cc.errs |= 4u;   // recomputed hit differs
-            cc.nodes += Q.nodes; cc.ptests += Q.ptests; cc.planes += Q.planes & 0x7fffffffu; cc.aux += Q.aux;
-            return id;
-        };
         pt::Ray ray;
         ray.o = pt::mk3(in[i].o[0], in[i].o[1], in[i].o[2]);
         ray.d = pt::mk3(in[i].d[0], in[i].d[1], in[i].d[2]);
         pt::Rng R = pt::rng_seed(in[i].seed);
-        const uint64_t rays0 = C.rays;
-        const pt::f3 L = pt::trace_path_with(V, q, ray, s->hs.depth, R, vs, C);
-        out[i] = pt_path_out{{L.x, L.y, L.z}, (uint32_t)(C.rays - rays0)};
+        const uint64_t rays0 = q.C.rays;
+        const pt::f3 L = pt::trace_path_with(V, q, ray, s->hs.depth, R, vs, q.C);
+        out[i] = pt_path_out{{L.x, L.y, L.z}, (uint32_t)(q.C.rays - rays0)};
     }
-    if (counters8) {
-        uint64_t c[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // (slots CTR_RAYS .. CTR_FALLBACKS_RAY)
-        c[pt::CTR_RAYS] = C.rays; c[pt::CTR_NODES] = C.nodes; c[pt::CTR_PTESTS] = C.ptests; c[pt::CTR_PLANES] = C.planes;
-        c[pt::CTR_ERRORS] = C.errs; c[pt::CTR_AUX] = C.aux; c[pt::CTR_FALLBACKS] = C.fallbacks;
-        c[pt::CTR_FALLBACKS_RAY] = exact_ray;
-        memcpy(counters8, c, sizeof(c));
-    }
-    return C.errs ? fail(PT_E_INVALID, "recomputed closest hit differs from the query's") : PT_OK;
+    q.pack(counters8);
+    return q.verdict();
 }
 
 int pt_selftest_pixels_host(pt_scene* s, uint64_t n, pt_pixel_state* state, const uint32_t* counts, uint32_t spp,
@@ -391,22 +385,8 @@ int pt_selftest_pixels_host(pt_scene* s, uint64_t n, pt_pixel_state* state, cons
     if (rc) return rc;
     const pt::SceneView V = host_view(s, PT_TRAVERSAL_REPLAY);
     const pt::CamView cam = make_cam(s);
-    HostStack stk;
+    HostQuery q(V);   // the pixel-sample engine's query
     HostVStore vs;
-    pt::Counts C{};
-    uint64_t exact_ray = 0;
-    // the pixel-sample engine's query (pt_query.h state machine), run to completion
-    auto q = [&](const pt::Ray& rr, pt::Hit& hh, pt::Counts& cc) {
-        pt::QCounts Q{};
-        uint32_t ex = 0;
-        const int id = pt::q_run(V, rr, stk, hh, Q, ex);
-        cc.fallbacks += ex;
-        const float w = pt::q_prep(V, rr).w;
-        if (w != w) exact_ray++;   // a non-finite ray (q_init_pre: Q_EXACT from the start)
-        if (Q.planes & 0x80000000u) cc.errs |= 4u;   // recomputed hit differs
-        cc.nodes += Q.nodes; cc.ptests += Q.ptests; cc.planes += Q.planes & 0x7fffffffu; cc.aux += Q.aux;
-        return id;
-    };
     for (uint64_t i = 0; i < n; ++i) {
         pt_pixel_state& P = state[i];
         const uint32_t count = counts ? counts[i] : spp;
@@ -418,21 +398,15 @@ int pt_selftest_pixels_host(pt_scene* s, uint64_t n, pt_pixel_state* state, cons
             const float fx = (float)P.x + pt::rng_uniform(R);
             const float fy = (float)P.y + pt::rng_uniform(R);
             const pt::Ray ray = pt::camera_ray(cam, fx, fy);
-            sum = sum + pt::trace_path_with(V, q, ray, s->hs.depth, R, vs, C);
+            sum = sum + pt::trace_path_with(V, q, ray, s->hs.depth, R, vs, q.C);
         }
         P.rng = pt::pixel_rng_word(R);
         P.saved = pt::pixel_rng_saved(R);
         P.sum[0] = sum.x; P.sum[1] = sum.y; P.sum[2] = sum.z;
         P.samples += count;
     }
-    if (counters8) {
-        uint64_t c[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // (slots CTR_RAYS .. CTR_FALLBACKS_RAY)
-        c[pt::CTR_RAYS] = C.rays; c[pt::CTR_NODES] = C.nodes; c[pt::CTR_PTESTS] = C.ptests; c[pt::CTR_PLANES] = C.planes;
-        c[pt::CTR_ERRORS] = C.errs; c[pt::CTR_AUX] = C.aux; c[pt::CTR_FALLBACKS] = C.fallbacks;
-        c[pt::CTR_FALLBACKS_RAY] = exact_ray;
-        memcpy(counters8, c, sizeof(c));
-    }
-    return C.errs ? fail(PT_E_INVALID, "recomputed closest hit differs from the query's") : PT_OK;
+    q.pack(counters8);
+    return q.verdict();
 }
 
 int pt_selftest_features_host(pt_scene* s, uint64_t n, const float* xy, pt_feature* out, uint64_t* counters8) {
@@ -442,28 +416,17 @@ int pt_selftest_features_host(pt_scene* s, uint64_t n, const float* xy, pt_featu
     if (rc) return rc;
     const pt::SceneView V = host_view(s, PT_TRAVERSAL_REPLAY);
     const pt::CamView cam = make_cam(s);
-    HostStack stk;
-    uint64_t c[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // (slots CTR_RAYS .. CTR_FALLBACKS_RAY)
+    HostQuery q(V);
     for (uint64_t i = 0; i < n; ++i) {
-        // k_feats' job on one thread: the position's ray, the query state machine run to completion
-        // (as pt_selftest_ray_intersection runs it), the record from the hit
-        const pt::Ray ray = pt::camera_ray(cam, xy[2 * i], xy[2 * i + 1]);
-        pt::QCounts Q{0u, 0u, 0u, 0u};
-        uint32_t ex = 0;
+        // k_feats' job on one thread: the position's ray, its query, the record from the hit
         pt::Hit h;
-        const int id = pt::q_run(V, ray, stk, h, Q, ex);
-        if (Q.planes & 0x80000000u) c[pt::CTR_ERRORS]++;   // recomputed hit differs
-        const float w = pt::q_prep(V, ray).w;
-        if (w != w) c[pt::CTR_FALLBACKS_RAY]++;   // a non-finite ray (q_init_pre: Q_EXACT from the start)
-        c[pt::CTR_RAYS]++;
-        c[pt::CTR_NODES] += Q.nodes; c[pt::CTR_PTESTS] += Q.ptests; c[pt::CTR_PLANES] += Q.planes & 0x7fffffffu;
-        c[pt::CTR_AUX] += Q.aux; c[pt::CTR_FALLBACKS] += ex;
+        const int id = q.query(pt::camera_ray(cam, xy[2 * i], xy[2 * i + 1]), h);
         pt::Feature f;
         pt::feature_fill(V, id, h, f);
         memcpy(out + i, &f, sizeof(f));
     }
-    if (counters8) memcpy(counters8, c, sizeof(c));
-    return c[pt::CTR_ERRORS] ? fail(PT_E_INVALID, "recomputed closest hit differs from the query's") : PT_OK;
+    q.pack(counters8);
+    return q.verdict();
 }
 
 int pt_selftest_fit_block(uint32_t aux_words, uint32_t dfs_words, uint32_t* block_aux_only, uint32_t* block_both,

@@ -579,6 +579,33 @@ int pt_session_stats(pt_session* ss, pt_stats* st) {
     return PT_OK;
 }
 
+}  // extern "C"
+
+namespace pti {
+static_assert(sizeof(pt_stats) == 40 * 8,
+              "pt_stats changed: give every new field its rule in merge_stats (sum, max, last value, or the render's own)");
+// A rank's statistics into the render's: the counts summed, the times the slowest rank's, the record
+// sizes any rank's.  (wall_ms, gather_rccl and gather_allocs are the render's own: pt_render sets them.)
+void merge_stats(pt_stats& into, const pt_stats& rank) {
+    into.rays += rank.rays; into.node_visits += rank.node_visits; into.prim_tests += rank.prim_tests;
+    into.plane_tests += rank.plane_tests; into.samples += rank.samples; into.errors += rank.errors;
+    into.aux_visits += rank.aux_visits; into.fallbacks += rank.fallbacks; into.fallbacks_ray += rank.fallbacks_ray;
+    into.isect_launches += rank.isect_launches; into.rounds += rank.rounds;
+    into.coop_rays += rank.coop_rays; into.coop_node_visits += rank.coop_node_visits;
+    into.coop_prim_tests += rank.coop_prim_tests; into.coop_aux_visits += rank.coop_aux_visits;
+    into.coop_launches += rank.coop_launches;
+    into.short_pixels += rank.short_pixels; into.handed_on += rank.handed_on;
+    for (int k = 0; k < PT_HO_N; ++k) into.handoff[k] += rank.handoff[k];
+    into.kernel_ms = std::max(into.kernel_ms, rank.kernel_ms);
+    into.resolve_ms = std::max(into.resolve_ms, rank.resolve_ms);
+    into.isect_ms = std::max(into.isect_ms, rank.isect_ms);
+    into.coop_ms = std::max(into.coop_ms, rank.coop_ms);
+    into.node_bytes = rank.node_bytes; into.prim_bytes = rank.prim_bytes; into.aux_bytes = rank.aux_bytes;
+}
+}  // namespace pti
+
+extern "C" {
+
 void* pt_session_stream(pt_session* ss) {
     if (!ss) return nullptr;
     (void)flush_trace(ss);   // work ordered after the stream sees every trace() so far (errors: pt_last_error)

@@ -288,6 +288,13 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _counters8(ctr):
+    """a host twin's counters8 (slots CTR_RAYS .. CTR_FALLBACKS_RAY), named as pt_stats names them"""
+    return {"rays": int(ctr[CTR_RAYS]), "node_visits": int(ctr[CTR_NODES]), "prim_tests": int(ctr[CTR_PTESTS]),
+            "plane_tests": int(ctr[CTR_PLANES]), "errors": int(ctr[CTR_ERRORS]), "aux_visits": int(ctr[CTR_AUX]),
+            "fallbacks": int(ctr[CTR_FALLBACKS]), "fallbacks_ray": int(ctr[CTR_FALLBACKS_RAY])}
+
+
 class Scene:
     """A loaded hw5 scene (owns the native pt_scene)."""
 
@@ -524,9 +531,7 @@ class Scene:
         out = np.zeros(len(paths), RADIANCE_DTYPE)
         ctr = np.zeros(8, np.uint64)
         _check(_lib.pt_selftest_paths_host(self._h, len(paths), _ptr(paths), _ptr(out), _ptr(ctr)))
-        return out, {"rays": int(ctr[CTR_RAYS]), "node_visits": int(ctr[CTR_NODES]), "prim_tests": int(ctr[CTR_PTESTS]),
-                     "plane_tests": int(ctr[CTR_PLANES]), "errors": int(ctr[CTR_ERRORS]), "aux_visits": int(ctr[CTR_AUX]),
-                     "fallbacks": int(ctr[CTR_FALLBACKS]), "fallbacks_ray": int(ctr[CTR_FALLBACKS_RAY])}
+        return out, _counters8(ctr)
 
     def selftest_pixels_host(self, state, counts=None, spp=0):
         """Scene.sample_pixels' records run on the host (camera_ray and trace_path_with over the query
@@ -535,10 +540,7 @@ class Scene:
         ctr = np.zeros(8, np.uint64)
         _check(_lib.pt_selftest_pixels_host(self._h, len(state), _ptr(state), _ptr(counts), spp, _ptr(ctr)))
         added = int(counts.sum(dtype=np.uint64)) if counts is not None else spp * len(state)
-        return state, {"rays": int(ctr[CTR_RAYS]), "node_visits": int(ctr[CTR_NODES]), "prim_tests": int(ctr[CTR_PTESTS]),
-                       "plane_tests": int(ctr[CTR_PLANES]), "errors": int(ctr[CTR_ERRORS]), "aux_visits": int(ctr[CTR_AUX]),
-                       "fallbacks": int(ctr[CTR_FALLBACKS]), "fallbacks_ray": int(ctr[CTR_FALLBACKS_RAY]),
-                       "samples": added}
+        return state, dict(_counters8(ctr), samples=added)
 
     def selftest_features(self, xy):
         """Scene.features' records computed on the host (camera_ray, the query state machine, the
@@ -547,9 +549,7 @@ class Scene:
         out = np.zeros(len(xy), FEATURE_DTYPE)
         ctr = np.zeros(8, np.uint64)
         _check(_lib.pt_selftest_features_host(self._h, len(xy), _ptr(xy), _ptr(out), _ptr(ctr)))
-        return out, {"rays": int(ctr[CTR_RAYS]), "node_visits": int(ctr[CTR_NODES]), "prim_tests": int(ctr[CTR_PTESTS]),
-                     "plane_tests": int(ctr[CTR_PLANES]), "errors": int(ctr[CTR_ERRORS]), "aux_visits": int(ctr[CTR_AUX]),
-                     "fallbacks": int(ctr[CTR_FALLBACKS]), "fallbacks_ray": int(ctr[CTR_FALLBACKS_RAY])}
+        return out, _counters8(ctr)
 
     def selftest_render_host(self, x0, y0, w, h, spp=0, traversal=TRAVERSAL_REPLAY):
         rad = np.zeros((h, w, 3), np.float32)

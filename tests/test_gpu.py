@@ -418,15 +418,18 @@ def test_render_ngpu_sessions_on_one_device(pt, cfg, ngpu, mode, monkeypatch):
     (rank g of n) and driving it -- the drop-in's own multi-GPU path -- run here with
     every session on device 0 (PT_TUNE same_device=1, framebuffer through the host;
     same_device=2: the ranks render one after another once all are set up).  The
-    gathered image and the summed ray count must equal the reference's (= ngpu 1)."""
+    gathered image and the summed ray count must equal the reference's (= ngpu 1), and
+    the summed sample count the one-GPU render's: every pixel's SAMPLES (every rank's
+    samples arrive in the merged stats)."""
     monkeypatch.setenv("PT_TUNE", "same_device=" + mode)
     full = M["full"][cfg]
     with pt.Scene.load(U.scene_path(cfg)) as s:
         rgb, _, st = s.render(ngpu=ngpu)
-        w, h = s.info["width"], s.info["height"]
+        w, h, spp = s.info["width"], s.info["height"], s.info["samples"]
     ppm = b"P6\n%d %d\n255\n" % (w, h) + rgb.tobytes()
     assert U.md5(ppm) == full["md5"]
     assert st["rays"] == full["rays"] and st["errors"] == 0 and st["gather_rccl"] == 0
+    assert st["samples"] == w * h * spp
 
 
 def test_render_ngpu_concurrent_sessions_repeated(pt, monkeypatch):

@@ -359,6 +359,19 @@ def test_render_without_gpu_fails_loudly():
         assert e.value.code in (pt.PT_E_NO_GPU, pt.PT_E_HIP)
 
 
+@pytest.mark.parametrize("ngpu", [2, 1])
+def test_rccl_gather_on_one_device_is_refused(ngpu, monkeypatch):
+    """PT_TUNE same_device puts every rank on one device, where RCCL cannot place two ranks:
+    GATHER_RCCL is then refused (PT_E_INVALID) before any session or device call -- so also
+    on a machine without a GPU --, not answered with PT_OK and an unwritten image."""
+    monkeypatch.setenv("PT_TUNE", "same_device=1")
+    with pt.Scene.load(U.scene_path("practice5_1.txt")) as s:
+        with pytest.raises(pt.PTError) as e:
+            s.render(ngpu=ngpu, gather=pt.GATHER_RCCL)
+        assert e.value.code == pt.PT_E_INVALID
+        assert "one device" in str(e.value)
+
+
 def test_device_init_without_gpu_fails_loudly():
     if U.gpu_available():
         pytest.skip("GPU present")
